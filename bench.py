@@ -11,12 +11,18 @@ N > 1 (--gpus N): the same configs[1] workload on every rank, one process per GP
 in the data path; value = all ranks' signatures / the max-over-ranks time (weak scaling, so the
 1/2/4/8 values form a same-workload series).  Without WORLD_SIZE in the environment, --gpus N
 spawns the N rank processes itself (before anything touches the GPU); torch.distributed.run
-launches them the same way.  The configs[2] firehose then runs as the `firehose` field: 16,777,216
+launches them the same way.  With --full the configs[2] firehose then runs as the `firehose` field: 16,777,216
 signatures (32-byte messages) sharded by contiguous 64-aligned index ranges over the ranks (strong
 scaling), verified as resident sub-shards, the verdict bitmaps merged once over gloo for the
 exact-bad-set check.
 
-Extra fields: roofline (dominant kernel) and roofline_per_kernel, cpu_baseline (the oracle's
+A plain run sets up, warms up, times the --steps steps, checks their verdicts and prints the result
+line (metric, value, unit, ms_per_step, ... of the timed region); everything below runs only with
+--full.  --dump-outputs DIR writes what the last timed step returned to its caller (the batch
+verdict and the per-signature verdicts) as float32 .npy files; the inputs are seeded, so two builds
+run with the same arguments can be compared output for output.
+
+Extra fields (--full): roofline (dominant kernel) and roofline_per_kernel, cpu_baseline (the oracle's
 batch verifier on the host's usable cores, rank 0, N = 1), host_to_host (pipelined verification of
 host-resident batches, PCIe included), latency of a 1,024-signature batch host -> host, the C3
 firehose on one GPU, the C1 / C4 / C5 legs with their CPU counterparts, and configs.BLS: the
@@ -47,6 +53,7 @@ sys.path.insert(0, ROOT)
 
 FIREHOSE_N = 16777216
 SUBSHARD = 2097152
+DUMP_MAX = 8388608  # --dump-outputs: float32 values per array at most (32 MB)
 
 # Algorithmic field multiplications (one 255-bit product: a 10 x 10 limb schoolbook = 100
 # v_mad_u64_u32; a squaring 55), counted on the host-emulation build
@@ -486,6 +493,28 @@ def run_headline_dry(args, rank, world, dist):
     return {"dt": dt, "dt_max": dt_max}
 
 
+def dump_outputs(path, allv, bits):
+    """--dump-outputs: what a caller of the timed path receives from its last step (Staged.fetch():
+    the batch verdict and the per-signature verdicts) as float32 arrays, one .npy file each.  The
+    inputs are seeded (synth), so the same arguments give the same files on every run and build."""
+    os.makedirs(path, exist_ok=True)
+    v = np.asarray(bits).astype(np.float32)
+    if v.size > DUMP_MAX:  # a fixed, seeded sample (sorted indices) keeps the files under 64 MB
+        v = v[np.sort(np.random.default_rng(7).choice(v.size, size=DUMP_MAX, replace=False))]
+    np.save(os.path.join(path, "batch_verdict.npy"), np.array([1.0 if allv else 0.0], dtype=np.float32))
+    np.save(os.path.join(path, "signature_verdicts.npy"), v)
+
+
+def tally_check(stages, runs):
+    """every run's batch verdict, graph replays included, as tallied on the device by the runs"""
+    acc = rej = 0
+    for s_ in stages:
+        a_, r_ = s_.run_tally()
+        acc, rej = acc + a_, rej + r_
+    if rej or acc != runs:
+        raise SystemExit(f"batch verdicts over the bench: {acc} accepted, {rej} rejected of {runs} runs")
+
+
 def run_headline(args, eng, rank, world, dist):
     from narwhal_amd import _lib
     pk, sg, msgs, offs, lens = synth(eng, args.n, args.msg_len, seed=1000 + rank, keys=args.keys)
@@ -497,10 +526,13 @@ def run_headline(args, eng, rank, world, dist):
         stages = [eng.stage(pk, sg, msgs, offs, lens) for _ in range(max(1, args.inflight))]
 
     def check_all(what):
+        got = []
         for s_ in stages:
             allv, bits = s_.fetch()
             if not (allv and bits.all()):
                 raise SystemExit(f"verification of a valid synthetic batch failed ({what})")
+            got.append((allv, bits))
+        return got
 
     # setup (untimed, not counted as warmup): every stage's first run allocates its MSM scratch
     # and captures its HIP graph; every verdict is checked
@@ -508,20 +540,23 @@ def run_headline(args, eng, rank, world, dist):
         s_.run(mode=args.mode)
     check_all("setup")
     dt, dt_max = timed_region(stages, args, dist, lambda st: st.run(mode=args.mode))  # seed None: OS entropy
-    check_all("timed region: last run of every stage")
+    got = check_all("timed region: last run of every stage")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *got[(args.steps - 1) % len(stages)])  # the last timed step's stage
+    if not args.full:
+        # a plain run ends here: the headline figure alone (the per-run verdict tally included)
+        if args.mode == 1:
+            tally_check(stages, len(stages) + args.warmup + args.steps)
+        for s_ in stages:
+            s_.free()
+        return {"dt": dt, "dt_max": dt_max}
     steady = steady_state(stages, args, lambda st: st.run(mode=args.mode))
     if steady is not None:
         steady["ramp_and_drain_cost"] = dt_max / (args.steps * steady["ms_per_step"] * 1e-3) - 1.0
         check_all("steady-state steps")
     if args.mode == 1:
         # every run's batch verdict, graph replays included, as tallied on the device by the runs
-        runs = len(stages) + args.warmup + args.steps + (steady["steps"] if steady else 0)
-        acc = rej = 0
-        for s_ in stages:
-            a_, r_ = s_.run_tally()
-            acc, rej = acc + a_, rej + r_
-        if rej or acc != runs:
-            raise SystemExit(f"batch verdicts over the bench: {acc} accepted, {rej} rejected of {runs} runs")
+        tally_check(stages, len(stages) + args.warmup + args.steps + (steady["steps"] if steady else 0))
     # single-stream pass: step latency and per-kernel device times without overlap
     st = stages[0]
     st.kernel_times(args.mode, reset=True)
@@ -814,7 +849,17 @@ def main():
     ap.add_argument("--headline-only", action="store_true",
                     help="only the timed headline steps (no 1K latency, host-to-host, configs or CPU baseline): "
                          "a rocprofv3 trace of this run is the headline alone")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, everything else the benchmark measures and checks (steady state, "
+                         "single stream, rooflines, 1K latency, host-to-host, CPU baselines, the other configs, "
+                         "BLS12-381; with --gpus N the firehose).  The options above that select or size these "
+                         "parts act only with --full; without it the run is the timed headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned to its caller as "
+                         "DIR/batch_verdict.npy and DIR/signature_verdicts.npy (float32; rank 0's with --gpus N)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # one process per GPU, started before anything touches the GPU (never an exec)
@@ -857,10 +902,12 @@ def main():
         if dist is None:
             raise SystemExit("NWV_BENCH_DRYRUN needs --gpus N > 1")
         h = run_headline_dry(args, rank, world, dist)
-        fire = run_firehose_dry(args, rank, world, dist)
+        fire = run_firehose_dry(args, rank, world, dist) if args.full else None
         if rank == 0:
             line = base_line(args, world, h["dt_max"])
-            line.update(dry_run=True, firehose=fire)
+            line.update(dry_run=True)
+            if args.full:
+                line.update(firehose=fire)
             line["config"]["workload"] += " -- DRY RUN: host stand-in steps, no GPU"
             print(json.dumps(line), flush=True)
         dist.destroy_process_group()
@@ -873,6 +920,14 @@ def main():
         # the same configs[1] workload as N = 1 on every rank (weak scaling: value = all ranks'
         # signatures / the max-over-ranks time), then the configs[2] firehose as an extra field
         h = run_headline(args, eng, rank, world, dist)
+        if not args.full:
+            if rank == 0:
+                line = base_line(args, world, h["dt_max"])
+                line.update(rank0_ms_per_step=h["dt"] / args.steps * 1e3)
+                print(json.dumps(line), flush=True)
+            eng.close()
+            dist.destroy_process_group()
+            return
         fire = run_firehose(args, eng, rank, world, dist)
         if rank == 0:
             line = base_line(args, world, h["dt_max"])
@@ -890,6 +945,10 @@ def main():
         return
 
     h = run_headline(args, eng, rank, world, dist)
+    if not args.full:
+        print(json.dumps(base_line(args, 1, h["dt"])), flush=True)
+        eng.close()
+        return
     dt, kt, stats = h["dt"], h["kt"], h["stats"]
     value = args.n * args.steps / dt
     threads = usable_cpus()

@@ -19,7 +19,7 @@ def test_bench_spawns_ranks_and_merges(gpus):
     env = dict(os.environ, NWV_BENCH_DRYRUN="1", NWV_BENCH_DRYRUN_N="200000")
     env.pop("WORLD_SIZE", None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--steps", "4",
-                        "--warmup", "1"], capture_output=True, text=True, timeout=300, env=env)
+                        "--warmup", "1", "--full"], capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout

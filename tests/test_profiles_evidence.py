@@ -1,6 +1,6 @@
 """The committed measurement evidence (SURVEY §8 d) is self-consistent: the newest kernel trace of
 the headline alone with ONE batch in flight (profiles/*_headline_inflight1_rocprof_kernel_stats.csv,
-rocprofv3 --kernel-trace --stats of `bench.py --headline-only --inflight 1`) reproduces the
+rocprofv3 --kernel-trace --stats of `bench.py --full --headline-only --inflight 1`) reproduces the
 single-stream kernel times of the bench line printed by that same run
 (*_headline_inflight1_bench_line.json) within 10 %, for the three kernels the roofline is read
 from.  The trace with 12 batches in flight is kept under its own name (*_inflight12_*): its

@@ -1,4 +1,4 @@
-"""GPU legs of BASELINE.json's other configs, measured beside the headline (bench.py --configs):
+"""GPU legs of BASELINE.json's other configs, measured beside the headline (bench.py --full):
 
   C1  Certificate::verify of a 4-node committee (header signature + 3 votes), host -> host, and
       verify_batch of 1,024 random signatures over 32-byte messages (p50 / p99);

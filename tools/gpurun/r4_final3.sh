@@ -17,7 +17,7 @@ bash tools/gpurun/r4_bls_prof.sh || exit $?
 cp gpurun_out/r4_bls_prof/bls_pmc_n16384.json profiles/round4_bls_pmc_n16384.json || exit $?
 timeout -k 10 120 python3 tools/bls_agg_probe.py 67 400 > $O/agg_probe.log 2>&1 || exit $?
 timeout -k 10 180 rocprofv3 --kernel-trace --stats -d $O/agg -o run --output-format csv -- python3 tools/bls_agg_probe.py 67 200 > $O/agg_trace.log 2>&1 || exit $?
-timeout -k 10 700 python -u bench.py > $O/bench.json 2> $O/bench.err || exit $?
-timeout -k 10 300 python -u bench.py --steps 20 --warmup 5 --no-configs --no-cpu-baseline > $O/bench_s20.json 2> $O/bench_s20.err || exit $?
-timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/prof -o b --output-format csv -- python3 bench.py --steps 20 --warmup 5 --headline-only --steady-steps 0 --single-steps 8 > $O/prof_bench.json 2> $O/prof.log || exit $?
+timeout -k 10 700 python -u bench.py --full > $O/bench.json 2> $O/bench.err || exit $?
+timeout -k 10 300 python -u bench.py --full --steps 20 --warmup 5 --no-configs --no-cpu-baseline > $O/bench_s20.json 2> $O/bench_s20.err || exit $?
+timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/prof -o b --output-format csv -- python3 bench.py --full --steps 20 --warmup 5 --headline-only --steady-steps 0 --single-steps 8 > $O/prof_bench.json 2> $O/prof.log || exit $?
 echo ALLDONE

@@ -8,7 +8,7 @@ O=gpurun_out/r4i
 mkdir -p $O
 for k in 4 6 8 12 16; do
   for rep in 1 2; do
-    timeout -k 10 200 python -u bench.py --steps 20 --warmup 5 --headline-only --inflight $k > $O/k${k}_r${rep}.json 2> $O/k${k}_r${rep}.err || exit $?
+    timeout -k 10 200 python -u bench.py --full --steps 20 --warmup 5 --headline-only --inflight $k > $O/k${k}_r${rep}.json 2> $O/k${k}_r${rep}.err || exit $?
   done
 done
 echo ALLDONE

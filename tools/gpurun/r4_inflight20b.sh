@@ -6,7 +6,7 @@ O=gpurun_out/r4i2
 mkdir -p $O
 for k in 20 24; do
   for q in 16 24; do
-    NWV_BENCH_HW_QUEUES=$q timeout -k 10 200 python -u bench.py --steps 20 --warmup 5 --headline-only --inflight $k > $O/k${k}_q${q}.json 2> $O/k${k}_q${q}.err || exit $?
+    NWV_BENCH_HW_QUEUES=$q timeout -k 10 200 python -u bench.py --full --steps 20 --warmup 5 --headline-only --inflight $k > $O/k${k}_q${q}.json 2> $O/k${k}_q${q}.err || exit $?
   done
 done
 echo ALLDONE

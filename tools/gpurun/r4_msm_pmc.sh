@@ -16,5 +16,5 @@ for n in 65536 2097152; do
   python3 tools/pmc_summary.py --n $n --note "round 4 at HEAD: rocprofv3 --pmc, 3 separate passes, tools/profile_driver.py --mode 1 (batch MSM), per-dispatch averages; FETCH_SIZE/WRITE_SIZE in KiB as reported (gfx950 FETCH_SIZE counts wide streaming reads at 1/2)" --out $O/round4_msm_pmc_n$n.json $O/n$n/p1 $O/n$n/p2 $O/n$n/p3 || exit $?
   cp $O/round4_msm_pmc_n$n.json profiles/ || exit $?
 done
-timeout -k 10 700 python -u bench.py > $O/bench.json 2> $O/bench.err || exit $?
+timeout -k 10 700 python -u bench.py --full > $O/bench.json 2> $O/bench.err || exit $?
 echo ALLDONE

@@ -11,8 +11,8 @@ cd "$GRAFT_REPO_ROOT"
 export TMPDIR=/tmp
 O=gpurun_out/r5ev
 mkdir -p $O
-timeout -k 10 700 python -u bench.py > $O/bench.json 2> $O/bench.err || exit $?
-timeout -k 10 300 python -u bench.py --steps 20 --warmup 5 > $O/bench_s20.json 2> $O/bench_s20.err || exit $?
-timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/prof1 -o b --output-format csv -- python3 bench.py --steps 20 --warmup 5 --headline-only --inflight 1 --steady-steps 0 --single-steps 8 > $O/headline_inflight1_bench_line.json 2> $O/prof1.log || exit $?
-timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/prof12 -o b --output-format csv -- python3 bench.py --steps 20 --warmup 5 --headline-only --inflight 12 --steady-steps 0 --single-steps 8 > $O/headline_inflight12_bench_line.json 2> $O/prof12.log || exit $?
+timeout -k 10 700 python -u bench.py --full > $O/bench.json 2> $O/bench.err || exit $?
+timeout -k 10 300 python -u bench.py --full --steps 20 --warmup 5 > $O/bench_s20.json 2> $O/bench_s20.err || exit $?
+timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/prof1 -o b --output-format csv -- python3 bench.py --full --steps 20 --warmup 5 --headline-only --inflight 1 --steady-steps 0 --single-steps 8 > $O/headline_inflight1_bench_line.json 2> $O/prof1.log || exit $?
+timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/prof12 -o b --output-format csv -- python3 bench.py --full --steps 20 --warmup 5 --headline-only --inflight 12 --steady-steps 0 --single-steps 8 > $O/headline_inflight12_bench_line.json 2> $O/prof12.log || exit $?
 echo ALLDONE

@@ -11,7 +11,7 @@ for mode in sdma blit; do
   timeout -k 10 120 python -u tools/c1_times.py 1000 > $O/${mode}_c1.json 2>> $O/err || exit $?
   timeout -k 10 120 python -u tools/lat1k.py 512 1000 > $O/${mode}_512.json 2>> $O/err || exit $?
   timeout -k 10 300 python -u tools/c4_times.py > $O/${mode}_c4.json 2>> $O/err || exit $?
-  timeout -k 10 200 python -u bench.py --headline-only --steps 20 --warmup 5 --no-cpu-baseline > $O/${mode}_s20.json 2>> $O/err || exit $?
+  timeout -k 10 200 python -u bench.py --full --headline-only --steps 20 --warmup 5 --no-cpu-baseline > $O/${mode}_s20.json 2>> $O/err || exit $?
 done
 unset HSA_ENABLE_SDMA
 timeout -k 10 120 python -u tools/c1_times.py 1000 > $O/sdma2_c1.json 2>> $O/err || exit $?

@@ -8,7 +8,7 @@ mkdir -p $O
 timeout -k 10 600 python -u -m pytest tests/test_gpu_msm.py tests/test_gpu_ed25519.py tests/test_gpu_baseline_configs.py tests/test_gpu_tail_timeout.py -m gpu -x -q --timeout 300 --timeout-method thread > $O/pytest.log 2>&1 || exit $?
 for r in 1 2 3; do
   for lib in libnwv.so libnwv_tailB.so; do
-    NWV_LIB=$lib timeout -k 10 200 python3 bench.py --headline-only --inflight 1 --steps 20 --warmup 5 --steady-steps 0 --single-steps 40 > $O/${lib}_$r.json 2> $O/${lib}_$r.err || exit $?
+    NWV_LIB=$lib timeout -k 10 200 python3 bench.py --full --headline-only --inflight 1 --steps 20 --warmup 5 --steady-steps 0 --single-steps 40 > $O/${lib}_$r.json 2> $O/${lib}_$r.err || exit $?
   done
 done
 for lib in libnwv.so libnwv_tailB.so; do
