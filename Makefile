@@ -37,7 +37,8 @@ narwhal_amd/lib/libnwv.so: narwhal_amd/lib/nwv_host.o narwhal_amd/lib/nwv_bls.o 
 oracle:
 	$(MAKE) -C oracle
 
-hostemu: tests/_build/libhostemu.so tests/_build/libsvcstub.so tests/_build/libblsemu.so tests/_build/libblsshard.so
+hostemu: tests/_build/libhostemu.so tests/_build/libsvcstub.so tests/_build/libblsemu.so tests/_build/libblsshard.so \
+	tests/_build/libcombemu.so
 # the BLS and Ed25519 calls' split over a multi-device context (bls_shard.h, shard.h) with stub per-device work
 tests/_build/libblsshard.so: tests/hostemu/bls_shard_stub.cpp narwhal_amd/csrc/bls_shard.h narwhal_amd/csrc/shard.h
 	@mkdir -p tests/_build
@@ -61,6 +62,10 @@ tests/_build/libsvcstub.so: tests/hostemu/service_stub.cpp narwhal_amd/csrc/nwv_
 tests/_build/libhostemu.so: tests/hostemu/hostemu.cpp $(CSRC)
 	@mkdir -p tests/_build
 	$(HIPCC) -std=c++17 -O1 --offload-host-only -x hip -DNWV_BOUNDS_CHECK -fPIC -shared -o $@ tests/hostemu/hostemu.cpp
+# the comb kernel's per-signature arithmetic on the host (tests/test_comb_hostemu.py)
+tests/_build/libcombemu.so: tests/hostemu/comb_hostemu.cpp $(CSRC)
+	@mkdir -p tests/_build
+	$(HIPCC) -std=c++17 -O1 --offload-host-only -x hip -DNWV_BOUNDS_CHECK -fPIC -shared -o $@ tests/hostemu/comb_hostemu.cpp
 
 tools: tools/ubench_valu tools/ubench_field tools/ubench_wave tools/ubench_row tools/ubench_prep tools/libsvcbench.so
 # native drivers of the C5 service leg (bench tooling): the service and the Core drain timed from C++ threads

@@ -88,7 +88,8 @@ typedef struct nwv_ctx nwv_ctx;
 #define NWV_FLAG_NO_FUSED_KEYSUM 2048u
 /* diagnostic / tests: a keyed batch of at most 64 signatures whose keys were all registered
  * (nwv_keycache_register: each key gets a fixed-base comb table) is checked in one launch,
- * signature by signature (k_ed_tiny); this flag sends it through the batch MSM instead */
+ * signature by signature (k_ed_tiny), and a larger one of at most nwv_comb_batch_max signatures
+ * by the comb kernel (k_ed_comb); this flag sends both through the batch MSM instead */
 #define NWV_FLAG_NO_TINY 4096u
 /* BLS12-381 calls of at most 1,024 items (the per-call paths) record the per-stage timing events
  * that nwv_bls_last_kernel_ms reports only with this flag: the events cost a single verification
@@ -107,6 +108,20 @@ int nwv_device_count(const nwv_ctx* ctx);
  * batches checked by the one-launch path (k_ed_tiny), out[1] batch MSMs, out[2] per-signature
  * passes (verify_each, or after a rejected MSM when verdict bits were asked for). */
 int nwv_diag_counters(const nwv_ctx* ctx, uint64_t out[3]);
+/* The same with room for later counters: writes the first min(cap, count) counters to out and
+ * returns their number, 4 (or an NWV_ERR_* code): the three of nwv_diag_counters, then out[3]
+ * registered-key batches checked by the comb kernel (k_ed_comb).  A comb batch counts in neither
+ * out[0] nor out[1], and never causes a per-signature pass. */
+int nwv_diag_counters_ex(const nwv_ctx* ctx, uint64_t* out, int cap);
+/* Largest keyed batch that takes the comb path: a single-device call of more than 64 and at most
+ * n signatures whose keys all have a comb table (nwv_keycache_register) is checked signature by
+ * signature in one launch of k_ed_comb -- exact ZIP-215 verdict bits, no random coefficients, no
+ * fallback pass after a rejection -- unless the context was opened with NWV_FLAG_NO_TINY,
+ * NWV_FLAG_MSM_ALWAYS or NWV_FLAG_MSM_NEVER.  0 turns the path off.  A call that splits over
+ * several devices keeps the batch MSM, so values at or above the shard minimum (NWV_SHARD_MIN,
+ * default 16,384) are clamped to just below it.  The getter returns the value in force. */
+int nwv_set_comb_batch_max(nwv_ctx* ctx, size_t n);
+size_t nwv_comb_batch_max(const nwv_ctx* ctx);
 /* HIP ordinal of the context's i-th device (-1 if out of range) */
 int nwv_device_ordinal(const nwv_ctx* ctx, int i);
 int nwv_abi_version(void);
@@ -166,7 +181,9 @@ int nwv_ed25519_verify_batch_keyed_digests(nwv_ctx* ctx, size_t n_pre, const uin
  * slot), so registering the committee gives its members' single verifies the cached form.  Each
  * registered key also gets a fixed-base comb table (i 16^j A, 64 KiB), which sends keyed batches
  * of at most 64 signatures by registered keys -- Certificate::verify, Header::verify,
- * Vote::verify -- through the one-launch path.  Registering the same key list again is a no-op.
+ * Vote::verify -- through the one-launch path, and larger ones of at most nwv_comb_batch_max
+ * signatures -- a large committee's certificate, a round's votes, validate_certificates --
+ * through the comb kernel.  Registering the same key list again is a no-op.
  * A full cache leaves further keys uncached; verdicts never depend on the cache. */
 int nwv_keycache_register(nwv_ctx* ctx, size_t n_keys, const uint8_t* keys);
 

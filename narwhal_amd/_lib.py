@@ -66,6 +66,9 @@ def load():
         "nwv_free": ([_vp], None),
         "nwv_device_count": ([_vp], _i32),
         "nwv_diag_counters": ([_vp, _vp], _i32),
+        "nwv_diag_counters_ex": ([_vp, _vp, _i32], _i32),
+        "nwv_set_comb_batch_max": ([_vp, _sz], _i32),
+        "nwv_comb_batch_max": ([_vp], _sz),
         "nwv_abi_version": ([], _i32),
         "nwv_last_error": ([], ctypes.c_char_p),
         "nwv_ed25519_verify_each": ([_vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp], _i32),
@@ -211,6 +214,23 @@ class Engine:
         out = np.zeros(3, dtype=np.uint64)
         _check(self.lib.nwv_diag_counters(self._h, out.ctypes.data))
         return {"tiny": int(out[0]), "msm": int(out[1]), "each": int(out[2])}
+
+    def diag_counters_ex(self):
+        """diag_counters plus 'comb': registered-key batches checked by the comb kernel"""
+        names = ("tiny", "msm", "each", "comb")
+        out = np.zeros(len(names), dtype=np.uint64)
+        k = self.lib.nwv_diag_counters_ex(self._h, out.ctypes.data, len(names))
+        if k < len(names):
+            _check(k if k < 0 else NWV_ERR_ARG)
+        return {nm: int(v) for nm, v in zip(names, out)}
+
+    def set_comb_batch_max(self, n):
+        """nwv_set_comb_batch_max: the largest registered-key batch that takes the comb path (0: off)"""
+        _check(self.lib.nwv_set_comb_batch_max(self._h, int(n)))
+
+    @property
+    def comb_batch_max(self):
+        return int(self.lib.nwv_comb_batch_max(self._h))
 
     def keycache_register(self, keys):
         """nwv_keycache_register: keys, a list of 32-byte keys (the committee, at epoch start)"""

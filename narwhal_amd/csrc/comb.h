@@ -1,0 +1,57 @@
+// comb.h -- lane-level pieces of the per-signature comb check (comb_kernels.hip k_ed_comb): the
+// equation of k_ed_tiny (tiny_kernels.hip), [8] R = [8]([s]B - [k]A) with [s]B - [k]A summed from
+// the fixed-base combs of B and of the registered key, for keyed batches above TINY_MAX.
+// Everything here is __host__ __device__: the kernel calls these functions and
+// tests/hostemu/comb_hostemu.cpp runs the same ones on the CPU.
+#pragma once
+#include "ed25519_lane.h"
+#include "msm.h"
+
+namespace nwv {
+
+// signatures a workgroup of k_ed_comb takes: hashing lanes, decompression rows, comb waves
+static constexpr int COMB_G = 4;
+
+// One signature's scalars: k = SHA-512(R || A || M) mod l and s, as the signed radix-16 digits
+// (msm.h comb_digits) that index the comb tables.  s >= l fails the signature (returns false) and
+// its digits, which would index past the tables, are zeroed.
+NWV_HD bool comb_scalars(const uint32_t Aw[8], const uint32_t Rw[8], const uint32_t Sw[8], const uint8_t* msg,
+                         uint32_t mlen, int ds[COMB_TABLES], int dk[COMB_TABLES]) {
+    uint32_t k[8], s[8];
+    const bool sok = lane_hash(Aw, Rw, Sw, msg, mlen, k) == FLAG_S_OK;
+    for (int q = 0; q < 8; q++) s[q] = sok ? Sw[q] : 0u;
+    comb_digits(s, ds);
+    comb_digits(k, dk);
+    return sok;
+}
+
+// Digit position j's term of [s]B - [k]A: entry |ds| of table j of B's comb with the sign of ds,
+// plus entry |dk| of table j of A's comb with the opposite sign of dk.
+NWV_HD ge_p3 comb_term(const uint32_t* bcomb, const uint32_t* acomb, int j, int ds, int dk) {
+    ge_p3 P = ge_p3_identity();
+    if (ds) {
+        const int m = ds < 0 ? -ds : ds;
+        P = ge_p1p1_to_p3(ge_madd(P, msm_load_point(bcomb + MSM_PT_WORDS * (COMB_ENTRIES * j + m - 1), ds < 0)));
+    }
+    if (dk) {
+        const int m = dk < 0 ? -dk : dk;
+        P = ge_p1p1_to_p3(ge_madd(P, msm_load_point(acomb + MSM_PT_WORDS * (COMB_ENTRIES * j + m - 1), dk > 0)));
+    }
+    return P;
+}
+
+// [8] R = [8] P projectively from p8 = X | Y | Z | T of [8] P (P3_WORDS words) and r8 = X | Y | Z
+// of [8] R (ten limbs each): cross product c of the four (P.X RZ, RX P.Z, P.Y RZ, RY P.Z) as
+// eight canonical words; the points are equal when products 0 and 1 and products 2 and 3 agree.
+NWV_HD void comb_cross(const uint32_t* p8, const uint32_t* r8, int c, uint32_t out[8]) {
+    const uint32_t* u = ((c & 1) ? r8 : p8) + (c < 2 ? 0 : 10);
+    const uint32_t* v = ((c & 1) ? p8 : r8) + 20;
+    fe_freeze(fe_mul(load_fe(u), load_fe(v)), out);
+}
+NWV_HD bool comb_cross_equal(const uint32_t x[32]) {
+    bool id = true;
+    for (int q = 0; q < 8; q++) id = id && x[q] == x[8 + q] && x[16 + q] == x[24 + q];
+    return id;
+}
+
+}  // namespace nwv

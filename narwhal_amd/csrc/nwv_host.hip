@@ -24,6 +24,7 @@
 #include "ed25519_kernels.hip"
 #include "msm_kernels.hip"
 #include "tiny_kernels.hip"
+#include "comb_kernels.hip"
 #include "shard.h"
 #include "stage_args.h"
 
@@ -145,16 +146,21 @@ struct EdBuffers {
     // one-launch path (k_ed_tiny) with each signature's key cache slot and comb table
     bool tiny = false;
     uint32_t tiny_slot[TINY_MAX], tiny_cidx[TINY_MAX];
+    // a keyed batch above TINY_MAX by registered keys that takes k_ed_comb (ed_stage_keyed): each
+    // signature's key cache slot and comb table, staged with the batch (views into the arena)
+    bool comb = false;
+    DevBuf comb_slot, comb_cidx;
     void release() {
         for (DevBuf* b : {&pk, &sig, &msg, &off, &len, &kbuf, &flags, &tables, &verdict, &m_scal,
                           &m_partial, &m_state, &m_pts, &m_digits, &m_cnt, &m_tiles, &m_entries,
                           &m_kstart, &m_hpart, &m_bsum, &m_wsum, &m_tpart, &m_ctr, &m_stamps, &m_mid, &m_kst2, &m_segkey, &keys, &koff, &ksig, &m_ascal,
-                          &kslot, &in})
+                          &kslot, &comb_slot, &comb_cidx, &in})
             b->release();
         nkeys_distinct = 0;
         kc_split = false;
         tables_ready = false;
         tiny = false;
+        comb = false;
     }
 };
 
@@ -192,6 +198,7 @@ struct Lane {
     // staged run's prep on this device) and chain_rec is recorded after it; null otherwise
     hipEvent_t chain_wait = nullptr, chain_rec = nullptr;
     DevBuf tiny_ws;  // k_ed_tiny's workspace (zeroed once; the kernel leaves it zeroed)
+    DevBuf comb_ws;  // k_ed_comb's (zeroed when it is allocated or grows; the kernel leaves it zeroed)
 };
 
 // Committee key cache of a device.  fastcrypto decompresses a public key once, when it is
@@ -256,8 +263,9 @@ struct Gpu {
     std::mutex chain_mu;
     std::vector<hipEvent_t> chain_ev;
     uint64_t chain_runs = 0;
-    // diagnostics (nwv_diag_counters): one-launch tiny batches, batch MSMs, per-signature passes
-    std::atomic<uint64_t> n_tiny{0}, n_msm{0}, n_each{0};
+    // diagnostics (nwv_diag_counters[_ex]): one-launch tiny batches, batch MSMs, per-signature
+    // passes, comb batches (k_ed_comb)
+    std::atomic<uint64_t> n_tiny{0}, n_msm{0}, n_each{0}, n_comb{0};
 };
 
 int with_device(Lane& d) {
@@ -287,6 +295,7 @@ void lane_close(Lane& d) {
     d.b2stage.release();
     d.b2dig.release();
     d.tiny_ws.release();
+    d.comb_ws.release();
     for (DevBuf* b : {&d.b2_base, &d.b2_off, &d.b2_len, &d.b2_out, &d.b2_packed, &d.b2_plen, &d.b2_err, &d.b2_in})
         b->release();
     if (d.stream) (void)hipStreamDestroy(d.stream);
@@ -969,6 +978,9 @@ struct KeyedTail {
     const uint32_t* koff;  // m + 1
     const uint32_t* ksig;  // n
     const uint32_t* kslot;  // m key cache slots, or null (uncached)
+    // k_ed_comb's per-signature tables (n key cache slots, n comb table indices), or null
+    const uint32_t* sig_slot = nullptr;
+    const uint32_t* sig_cidx = nullptr;
 };
 
 int ed_stage(Lane& d, EdBuffers& b, size_t lo, size_t hi, const uint8_t* pk, const uint8_t* sig,
@@ -996,7 +1008,10 @@ int ed_stage(Lane& d, EdBuffers& b, size_t lo, size_t hi, const uint8_t* pk, con
     const size_t m = kt ? kt->m : 0;
     const size_t o_koff = o_keys + (kt ? up(32 * m + 32) : 0), o_ksig = o_koff + (kt ? up(4 * m + 8) : 0);
     const size_t o_kslot = o_ksig + (kt ? up(4 * n + 8) : 0);
-    const size_t total = o_kslot + (kt && kt->kslot ? up(4 * m + 8) : 0);
+    const bool comb = kt && kt->sig_slot && kt->sig_cidx;
+    const size_t o_cslot = o_kslot + (kt && kt->kslot ? up(4 * m + 8) : 0);
+    const size_t o_ccidx = o_cslot + (comb ? up(4 * n + 8) : 0);
+    const size_t total = o_ccidx + (comb ? up(4 * n + 8) : 0);
     int rc;
     if ((rc = b.in.ensure(total))) return rc;
     // views into the arena are stale once it may have moved: drop the ones not re-pointed below
@@ -1007,6 +1022,9 @@ int ed_stage(Lane& d, EdBuffers& b, size_t lo, size_t hi, const uint8_t* pk, con
         for (DevBuf* v : {&b.keys, &b.koff, &b.ksig})
             if (v->view) v->release();
     if ((!kt || !kt->kslot) && b.kslot.view) b.kslot.release();
+    if (!comb)
+        for (DevBuf* v : {&b.comb_slot, &b.comb_cidx})
+            if (v->view) v->release();
     if (!inputs && ((rc = b.pk.ensure(32 * n + 16)) || (rc = b.sig.ensure(64 * n + 16)))) return rc;
     // the previous call's copy must have left the pinned buffer before it is rewritten
     htrace("stage:ensure");
@@ -1016,6 +1034,7 @@ int ed_stage(Lane& d, EdBuffers& b, size_t lo, size_t hi, const uint8_t* pk, con
     d.pksig_pending = false;
     b.tables_ready = false;
     b.tiny = false;
+    b.comb = false;
     // large stagings: the caller's pk / sig / message bytes are packed piece by piece with each
     // piece's DMA queued at once (pack_copy_h2d); the small computed regions go first
     const bool piped = 96 * (inputs ? n : 0) + mbytes >= ((size_t)16 << 20);
@@ -1035,6 +1054,10 @@ int ed_stage(Lane& d, EdBuffers& b, size_t lo, size_t hi, const uint8_t* pk, con
         std::memcpy(h + o_koff, kt->koff, 4 * (m + 1));
         if (n) std::memcpy(h + o_ksig, kt->ksig, 4 * n);
         if (kt->kslot) std::memcpy(h + o_kslot, kt->kslot, 4 * m);
+        if (comb) {
+            std::memcpy(h + o_cslot, kt->sig_slot, 4 * n);
+            std::memcpy(h + o_ccidx, kt->sig_cidx, 4 * n);
+        }
     }
     htrace("stage:packed");
     if (piped) {
@@ -1084,9 +1107,14 @@ int ed_stage(Lane& d, EdBuffers& b, size_t lo, size_t hi, const uint8_t* pk, con
         b.koff.set_view(g + o_koff, 4 * m + 8);
         b.ksig.set_view(g + o_ksig, 4 * n + 8);
         if (kt->kslot) b.kslot.set_view(g + o_kslot, 4 * m + 8);
+        if (comb) {
+            b.comb_slot.set_view(g + o_cslot, 4 * n + 8);
+            b.comb_cidx.set_view(g + o_ccidx, 4 * n + 8);
+        }
     }
     b.nkeys_distinct = m;
     b.kc_split = kt && kt->kslot && m;
+    b.comb = comb;
     return NWV_OK;
 }
 
@@ -1202,7 +1230,7 @@ int keycache_slots(Lane& d, const uint8_t* keys, size_t m, std::vector<uint32_t>
 int ed_stage_keyed(Lane& d, EdBuffers& b, size_t lo, size_t hi, size_t n_keys, const uint8_t* keys,
                    const uint32_t* key_idx, const uint8_t* sig, const uint8_t* msg_base,
                    const uint64_t* msg_off, const uint32_t* msg_len, const uint8_t* seed32,
-                   const DevBuf* dev_msg = nullptr, bool kc_lookup_only = false) {
+                   const DevBuf* dev_msg = nullptr, bool kc_lookup_only = false, size_t comb_max = 0) {
     const size_t n = hi - lo;
     // per-thread scratch reused across calls (fresh large vectors are page-faulted in every call)
     thread_local std::vector<uint32_t> local, cnt, kid, koff, ksig, cur;
@@ -1233,7 +1261,29 @@ int ed_stage_keyed(Lane& d, EdBuffers& b, size_t lo, size_t hi, size_t n_keys, c
     thread_local std::vector<uint32_t> kslot;
     int rc = keycache_slots(d, klist.data(), m, kslot, kc_lookup_only);
     if (rc) return rc;
-    const KeyedTail kt{klist.data(), m, koff.data(), ksig.data(), kslot.empty() ? nullptr : kslot.data()};
+    KeyedTail kt{klist.data(), m, koff.data(), ksig.data(), kslot.empty() ? nullptr : kslot.data()};
+    // the comb path (k_ed_comb): above TINY_MAX and at most comb_max signatures (0: the caller does
+    // not offer it), every key registered (comb table present), no flag that forces a path
+    thread_local std::vector<uint32_t> sig_slot, sig_cidx;
+    if (n > (size_t)TINY_MAX && n <= comb_max && !kslot.empty() &&
+        !(d.flags & (NWV_FLAG_NO_TINY | NWV_FLAG_MSM_ALWAYS | NWV_FLAG_MSM_NEVER))) {
+        KeyCache& kc = d.gpu->kc;
+        std::lock_guard<std::mutex> g(kc.mu);
+        bool all = !kc.comb_of.empty();
+        sig_slot.resize(n);
+        sig_cidx.resize(n);
+        for (size_t i = 0; i < n && all; i++) {
+            const uint32_t sl = kslot[kid[i]];
+            const uint32_t c = sl < kc.comb_of.size() ? kc.comb_of[sl] : UINT32_MAX;
+            all = c != UINT32_MAX && sl < kc.cap && c < kc.comb_cap;
+            sig_slot[i] = sl;
+            sig_cidx[i] = c;
+        }
+        if (all) {
+            kt.sig_slot = sig_slot.data();
+            kt.sig_cidx = sig_cidx.data();
+        }
+    }
     rc = ed_stage(d, b, 0, n, pk.data(), sig + 64 * lo, msg_base, msg_off + lo, msg_len + lo, seed32, &kt, dev_msg);
     if (rc) return rc;
     // the one-launch path: few signatures, every key registered (comb table present)
@@ -1265,12 +1315,22 @@ bool verdicts_all_valid(const uint64_t* bits, size_t n) {
 
 }  // namespace
 
+// Largest registered-key batch that takes the comb path by default, from the sweep of
+// tools/comb_sweep.py (profiles/comb_batch_sweep.json): the largest swept size up to
+// which k_ed_comb beat the batch MSM by the margin at every size.  0: the path is opt-in.
+#ifndef NWV_COMB_BATCH_MAX_DEFAULT
+#define NWV_COMB_BATCH_MAX_DEFAULT 2048
+#endif
+
 struct nwv_ctx {
     std::vector<Gpu*> devs;
     // a call splits over the devices only into ranges of at least this many signatures
     // (shard.h; env NWV_SHARD_MIN, read at nwv_init)
     size_t shard_min = 16384;
     size_t b2_shard_min = 4096;  // the same for BLAKE2b digest calls (messages; NWV_B2_SHARD_MIN)
+    // registered-key batches of TINY_MAX < n <= comb_batch_max signatures take k_ed_comb
+    // (nwv_set_comb_batch_max; 0: off; always below shard_min, so only single-range calls)
+    std::atomic<size_t> comb_batch_max{NWV_COMB_BATCH_MAX_DEFAULT};
 };
 
 // Per-kernel device time of the staged pipelines (HIP events on the batch's own stream).
@@ -1352,6 +1412,7 @@ static int init_devices(nwv_ctx** out, std::vector<int> ordinals, uint32_t flags
     if (!ctx) return set_err(NWV_ERR_OOM, "context allocation");
     ctx->shard_min = env_size("NWV_SHARD_MIN", ctx->shard_min, 1, SIZE_MAX);
     ctx->b2_shard_min = env_size("NWV_B2_SHARD_MIN", ctx->b2_shard_min, 1, SIZE_MAX);
+    ctx->comb_batch_max = std::min<size_t>(NWV_COMB_BATCH_MAX_DEFAULT, ctx->shard_min - 1);
     const size_t replicas = env_size("NWV_DEVICE_REPLICAS", 1, 1, 8);
     for (int o : ordinals)
         for (size_t r = 0; r < replicas; r++) {
@@ -1409,6 +1470,24 @@ int nwv_diag_counters(const nwv_ctx* ctx, uint64_t out[3]) {
     }
     return NWV_OK;
 }
+int nwv_diag_counters_ex(const nwv_ctx* ctx, uint64_t* out, int cap) {
+    if (!ctx || (cap > 0 && !out) || cap < 0) return set_err(NWV_ERR_ARG, "bad argument");
+    uint64_t v[4] = {0, 0, 0, 0};
+    for (const Gpu* g : ctx->devs) {
+        v[0] += g->n_tiny.load();
+        v[1] += g->n_msm.load();
+        v[2] += g->n_each.load();
+        v[3] += g->n_comb.load();
+    }
+    for (int k = 0; k < cap && k < 4; k++) out[k] = v[k];
+    return 4;
+}
+int nwv_set_comb_batch_max(nwv_ctx* ctx, size_t n) {
+    if (!ctx) return set_err(NWV_ERR_ARG, "null context");
+    ctx->comb_batch_max = std::min<size_t>(n, ctx->shard_min - 1);
+    return NWV_OK;
+}
+size_t nwv_comb_batch_max(const nwv_ctx* ctx) { return ctx ? ctx->comb_batch_max.load() : 0; }
 int nwv_device_ordinal(const nwv_ctx* ctx, int i) {
     return (ctx && i >= 0 && i < (int)ctx->devs.size()) ? ctx->devs[i]->ordinal : -1;
 }
@@ -1575,15 +1654,93 @@ static int tiny_on_device(Lane& d, EdBuffers& b, size_t n, hipStream_t stream, i
     return NWV_OK;
 }
 
+// k_ed_comb over a staged registered-key batch above TINY_MAX (b.comb): every signature's exact
+// verdict in one launch.  The batch verdict comes back through the lane's polled host word (or
+// the workspace when the lane has none); the verdict words are copied back only for a rejected
+// batch whose caller asked for them.
+static int comb_on_device(Lane& d, EdBuffers& b, size_t n, hipStream_t stream, int* ok, uint64_t* bits) {
+    int rc;
+    const size_t words = (n + 63) / 64;
+    // workspace: 64 bytes (arrivals, batch verdict), the accumulated words, the result words
+    const size_t need = 64 + 16 * words;
+    if (need > d.comb_ws.cap) {
+        if ((rc = d.comb_ws.ensure(need))) return rc;
+        NWV_HIP(hipMemsetAsync(d.comb_ws.p, 0, d.comb_ws.cap, stream));
+    }
+    const size_t wcap = (d.comb_ws.cap - 64) / 16;
+    static const bool no_poll = std::getenv("NWV_NO_HOST_POLL") != nullptr;
+    uint32_t* hv = (!no_poll && stream == d.stream) ? d.hword : nullptr;
+    CombArgs a{};
+    a.pk = b.pk.as<uint8_t>();
+    a.sig = b.sig.as<uint8_t>();
+    a.msg = b.msg.as<uint8_t>();
+    a.off = b.off.as<uint64_t>();
+    a.len = b.len.as<uint32_t>();
+    a.kc = d.gpu->kc.recs.as<uint32_t>();
+    a.combs = d.gpu->kc.combs.as<uint32_t>();
+    a.bcomb = d.gpu->comb.as<uint32_t>();
+    a.kslot = b.comb_slot.as<uint32_t>();
+    a.cidx = b.comb_cidx.as<uint32_t>();
+    a.ws = d.comb_ws.as<uint32_t>();
+    a.acc = reinterpret_cast<unsigned long long*>(d.comb_ws.as<uint8_t>() + 64);
+    a.bits = a.acc + wcap;
+    a.hword = hv;
+    a.n = (uint32_t)n;
+    d.hseq = (d.hseq + 1) & 0x3FFFFFFFu;  // (the workspace's verdict word carries it too)
+    if (d.hseq == 0) d.hseq = 1;
+    a.hseq = d.hseq;
+    if (hv) __atomic_store_n(hv, 0u, __ATOMIC_RELEASE);
+    hipLaunchKernelGGL(k_ed_comb, dim3((unsigned)((n + COMB_G - 1) / COMB_G)), dim3(64 * COMB_WAVES), 0, stream, a);
+    if (hipGetLastError() != hipSuccess) {
+        (void)hipStreamSynchronize(stream);
+        return set_err(NWV_ERR_HIP, "k_ed_comb launch");
+    }
+    uint32_t code = 0;
+    if (hv) {
+        uint32_t v = 0;
+        const auto t0 = std::chrono::steady_clock::now();
+        for (uint64_t k = 0; ((v = __atomic_load_n(hv, __ATOMIC_ACQUIRE)) >> 2) != a.hseq; k++) {
+            if ((k & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) break;
+            __builtin_ia32_pause();
+        }
+        NWV_HIP(hipStreamSynchronize(stream));
+        if ((v >> 2) == a.hseq) code = v & 3u;
+    }
+    if (code != 1u && code != 2u) {
+        uint32_t r[2] = {0, 0};
+        NWV_HIP(hipMemcpyAsync(r, a.ws, 8, hipMemcpyDeviceToHost, stream));
+        NWV_HIP(hipStreamSynchronize(stream));
+        code = (r[1] >> 2) == a.hseq ? (r[1] & 3u) : 0u;
+        if (code != 1u && code != 2u) return set_err(NWV_ERR_HIP, "k_ed_comb left no verdict");
+    }
+    htrace("batch:comb-done");
+    *ok = code == 1u ? 1 : 0;
+    if (bits) {
+        if (*ok) {
+            std::memset(bits, 0, 8 * words);
+            set_ones(bits, 0, n);
+        } else {
+            NWV_HIP(hipMemcpyAsync(bits, a.bits, 8 * words, hipMemcpyDeviceToHost, stream));
+            NWV_HIP(hipStreamSynchronize(stream));
+        }
+    }
+    return NWV_OK;
+}
+
 // Batch verdict of resident buffers: MSM, then (only if it rejects) the per-signature fallback
 // for the exact bad set.  bits: the shard's verdict words (may be null).  A tiny keyed batch by
-// registered keys takes the one-launch per-signature path instead (exact bits, no fallback).
+// registered keys takes the one-launch per-signature path instead (exact bits, no fallback), and
+// a larger one staged for it (b.comb) the comb path, k_ed_comb.
 static int batch_on_device(Lane& d, EdBuffers& b, size_t n, const uint8_t seed[32], hipStream_t stream,
                            int* ok, uint64_t* bits, bool state_ready = false) {
     int rc;
     if (b.tiny && n <= (size_t)TINY_MAX) {
         d.gpu->n_tiny++;
         return tiny_on_device(d, b, n, stream, ok, bits);
+    }
+    if (b.comb && n > (size_t)TINY_MAX) {
+        d.gpu->n_comb++;
+        return comb_on_device(d, b, n, stream, ok, bits);
     }
     const bool use_msm = (d.flags & NWV_FLAG_MSM_ALWAYS) ||
                          (!(d.flags & NWV_FLAG_MSM_NEVER) && n >= msm_min_n());
@@ -1731,12 +1888,16 @@ static int verify_batch_keyed_impl(nwv_ctx* ctx, size_t n_keys, const uint8_t* k
     uint8_t seed[32];
     fill_seed(seed32, seed);
     std::mutex omu;
+    // the comb path is offered to single-range calls only: a call that splits over the devices
+    // keeps the MSM on every shard
+    const size_t comb_max =
+        nwv::ed_shard_ranges(n, ctx->devs.size(), ctx->shard_min).size() == 1 ? ctx->comb_batch_max.load() : 0;
     return for_shards(ctx, n, [&](Lane& d, size_t lo, size_t hi) -> int {
         uint8_t s2[32];
         std::memcpy(s2, seed, 32);
         for (int k = 0; k < 8; k++) s2[24 + k] ^= (uint8_t)((uint64_t)lo >> (8 * k));
         int r = ed_stage_keyed(d, d.ed, lo, hi, n_keys, keys, key_idx, sig, msg_base, msg_off, msg_len, s2,
-                               nullptr, kc_lookup_only);
+                               nullptr, kc_lookup_only, comb_max);
         if (r) return r;
         int ok = 1;
         r = batch_on_device(d, d.ed, hi - lo, s2, d.stream, &ok,
@@ -2437,7 +2598,7 @@ int nwv_ed25519_verify_batch_keyed_digests(nwv_ctx* ctx, size_t n_pre, const uin
     // the batch is staged before the hash launch (its copy does not depend on the digests), so
     // hash and verification run back to back; no host round trip between them
     rc = ed_stage_keyed(d, d.ed, 0, n, n_keys, keys, key_idx, sig, nullptr, moff.data(), mlen.data(), seed,
-                        &d.b2_out);
+                        &d.b2_out, false, ctx->comb_batch_max.load());  // (a single range, see above)
     if (rc) return rc;
     // the hash also writes the digests straight into coherent pinned host memory (no copy back)
     if ((rc = d.b2dig.ensure(32 * n_pre, hipHostMallocCoherent | hipHostMallocMapped))) return rc;

@@ -178,6 +178,9 @@ extern "C" {
     pub fn nwv_free(ctx: *mut NwvCtx);
     pub fn nwv_device_count(ctx: *const NwvCtx) -> c_int;
     pub fn nwv_diag_counters(ctx: *const NwvCtx, out: *mut u64) -> c_int;
+    pub fn nwv_diag_counters_ex(ctx: *const NwvCtx, out: *mut u64, cap: c_int) -> c_int;
+    pub fn nwv_set_comb_batch_max(ctx: *mut NwvCtx, n: usize) -> c_int;
+    pub fn nwv_comb_batch_max(ctx: *const NwvCtx) -> usize;
     pub fn nwv_device_ordinal(ctx: *const NwvCtx, i: c_int) -> c_int;
     pub fn nwv_abi_version() -> c_int;
     pub fn nwv_last_error() -> *const c_char;
