@@ -38,7 +38,7 @@ oracle:
 	$(MAKE) -C oracle
 
 hostemu: tests/_build/libhostemu.so tests/_build/libsvcstub.so tests/_build/libblsemu.so tests/_build/libblsshard.so \
-	tests/_build/libcombemu.so
+	tests/_build/libcombemu.so tests/_build/libfeseeded.so
 # the BLS and Ed25519 calls' split over a multi-device context (bls_shard.h, shard.h) with stub per-device work
 tests/_build/libblsshard.so: tests/hostemu/bls_shard_stub.cpp narwhal_amd/csrc/bls_shard.h narwhal_amd/csrc/shard.h
 	@mkdir -p tests/_build
@@ -66,8 +66,17 @@ tests/_build/libhostemu.so: tests/hostemu/hostemu.cpp $(CSRC)
 tests/_build/libcombemu.so: tests/hostemu/comb_hostemu.cpp $(CSRC)
 	@mkdir -p tests/_build
 	$(HIPCC) -std=c++17 -O1 --offload-host-only -x hip -DNWV_BOUNDS_CHECK -fPIC -shared -o $@ tests/hostemu/comb_hostemu.cpp
+# fe25519.h's multiply and squaring in every column-sum form, column sums asserted below 2^63
+# (tests/test_fe_seeded_hostemu.py)
+tests/_build/libfeseeded.so: tests/hostemu/fe_seeded_hostemu.cpp narwhal_amd/csrc/fe25519.h
+	@mkdir -p tests/_build
+	$(HIPCC) -std=c++17 -O1 --offload-host-only -x hip -DNWV_BOUNDS_CHECK -fPIC -shared -o $@ tests/hostemu/fe_seeded_hostemu.cpp
 
-tools: tools/ubench_valu tools/ubench_field tools/ubench_wave tools/ubench_row tools/ubench_prep tools/libsvcbench.so
+tools: tools/ubench_valu tools/ubench_field tools/ubench_wave tools/ubench_row tools/ubench_prep tools/libsvcbench.so \
+	tools/fe_vectors
+# the device's fe_mul / fe_sq / fe_sqn on limb vectors from a file (tests/test_gpu_fe_seeded.py)
+tools/fe_vectors: tools/fe_vectors.hip narwhal_amd/csrc/fe25519.h
+	$(HIPCC) --offload-arch=$(ARCH) -O3 -std=c++17 -o $@ $<
 # native drivers of the C5 service leg (bench tooling): the service and the Core drain timed from C++ threads
 tools/libsvcbench.so: tools/svcbench.cpp narwhal_amd/lib/libnwv.so include/nwv.h include/nwv_types.h include/nwv_service.h
 	g++ -O2 -std=c++17 -fPIC -shared -pthread -Wall -o $@ $< -Lnarwhal_amd/lib -lnwv -Wl,-rpath,'$$ORIGIN/../narwhal_amd/lib'

@@ -1,7 +1,6 @@
 // fe25519.h -- GF(2^255-19) arithmetic for gfx950 VALU, radix 2^25.5 (ten 32-bit limbs).
 //
-// Replaces the field layer of curve25519-dalek-ng 4.1.1 (u64_backend, radix 2^51,
-// /root/reference/workspace-hack/Cargo.toml:91).  On CDNA4 the natural multiply is the
+// Replaces the field layer of curve25519-dalek-ng 4.1.1 (u64_backend, radix 2^51).  On CDNA4 the natural multiply is the
 // 32x32->64 multiply-accumulate `v_mad_u64_u32`, so limbs are 26/25 bits wide and a
 // product is 100 multiply-adds into ten 64-bit column accumulators.  Everything here is
 // __host__ __device__ so a test-only host build (tests/hostemu) can run it with limb-bound
@@ -131,9 +130,218 @@ NWV_HD fe fe_carry64(uint64_t h[10]) {
 
 NWV_HD uint64_t mad(uint32_t a, uint32_t b, uint64_t c) { return (uint64_t)a * b + c; }
 
-// h = f * g.  Column k collects f_i g_j with i + j = k (mod 10); the term is doubled when
-// i and j are both odd (radix 2^25.5) and multiplied by 19 when i + j >= 10 (2^255 = 19).
-NWV_HD fe fe_mul(const fe& f, const fe& g) {
+// a * b + c as one v_mad_u64_u32 the optimiser cannot take apart: a column sum that starts from
+// the carry of the column below keeps that carry as the 64-bit addend of its first multiply-add
+// (LLVM otherwise reassociates the sum and adds the carry with a v_lshl_add_u64 of its own).
+// The host path is the same arithmetic in plain C++.
+// The compiler pads an asm statement that names a register a recent asm statement wrote with
+// s_nop, so the interleaved chains of a product write their (unused) carry-outs to different
+// registers: chain 0 to vcc, the others each to an SGPR pair of its own (`sink`, kept live
+// through the chain so that no two chains are given the same pair).
+template <int CHAIN>
+NWV_HD uint64_t mad_pin(uint32_t a, uint32_t b, uint64_t c, uint64_t& sink) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    uint64_t d;
+    if constexpr (CHAIN == 0)
+        asm("v_mad_u64_u32 %0, vcc, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c) : "vcc");
+    else
+        asm("v_mad_u64_u32 %0, %1, %2, %3, %4" : "=v"(d), "+s"(sink) : "v"(a), "v"(b), "v"(c));
+    return d;
+#else
+    (void)sink;
+    return (uint64_t)a * b + c;
+#endif
+}
+
+// acc + a[0] b[0] + ... + a[n-1] b[n-1] as n dependent v_mad_u64_u32 in ONE asm statement (a
+// whole column sum): the compiler pads between asm statements, never inside one, and the
+// hardware interlocks a multiply-add on the one before it.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define NWV_MAD1(A, B) "v_mad_u64_u32 %0, vcc, %" #A ", %" #B ", %0\n\t"
+#define NWV_AB(t) "v"(a[t]), "v"(b[t])
+#endif
+NWV_HD uint64_t mad_col(int n, const uint32_t* a, const uint32_t* b, uint64_t acc) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    switch (n) {  // n is a constant after unrolling
+        case 4:
+            asm(NWV_MAD1(1, 2) NWV_MAD1(3, 4) NWV_MAD1(5, 6) NWV_MAD1(7, 8)
+                : "+v"(acc) : NWV_AB(0), NWV_AB(1), NWV_AB(2), NWV_AB(3) : "vcc");
+            break;
+        case 5:
+            asm(NWV_MAD1(1, 2) NWV_MAD1(3, 4) NWV_MAD1(5, 6) NWV_MAD1(7, 8) NWV_MAD1(9, 10)
+                : "+v"(acc) : NWV_AB(0), NWV_AB(1), NWV_AB(2), NWV_AB(3), NWV_AB(4) : "vcc");
+            break;
+        case 6:
+            asm(NWV_MAD1(1, 2) NWV_MAD1(3, 4) NWV_MAD1(5, 6) NWV_MAD1(7, 8) NWV_MAD1(9, 10) NWV_MAD1(11, 12)
+                : "+v"(acc) : NWV_AB(0), NWV_AB(1), NWV_AB(2), NWV_AB(3), NWV_AB(4), NWV_AB(5) : "vcc");
+            break;
+        case 9:
+            asm(NWV_MAD1(1, 2) NWV_MAD1(3, 4) NWV_MAD1(5, 6) NWV_MAD1(7, 8) NWV_MAD1(9, 10) NWV_MAD1(11, 12)
+                NWV_MAD1(13, 14) NWV_MAD1(15, 16) NWV_MAD1(17, 18)
+                : "+v"(acc)
+                : NWV_AB(0), NWV_AB(1), NWV_AB(2), NWV_AB(3), NWV_AB(4), NWV_AB(5), NWV_AB(6), NWV_AB(7), NWV_AB(8)
+                : "vcc");
+            break;
+        case 10:
+            asm(NWV_MAD1(1, 2) NWV_MAD1(3, 4) NWV_MAD1(5, 6) NWV_MAD1(7, 8) NWV_MAD1(9, 10) NWV_MAD1(11, 12)
+                NWV_MAD1(13, 14) NWV_MAD1(15, 16) NWV_MAD1(17, 18) NWV_MAD1(19, 20)
+                : "+v"(acc)
+                : NWV_AB(0), NWV_AB(1), NWV_AB(2), NWV_AB(3), NWV_AB(4), NWV_AB(5), NWV_AB(6), NWV_AB(7), NWV_AB(8),
+                  NWV_AB(9)
+                : "vcc");
+            break;
+        default:
+            __builtin_trap();  // no column of a product has another length
+    }
+    return acc;
+#else
+    for (int t = 0; t < n; t++) acc += (uint64_t)a[t] * b[t];
+    return acc;
+#endif
+}
+
+// How the ten column sums of a product are accumulated and carried (measured by
+// tools/ubench_field):
+//   FE_COLS_PLAIN   ten independent sums, then fe_carry64 adds each carry into the next sum
+//   FE_COLS_SERIAL  one chain 0 -> 1 -> ... -> 9: every sum but the first starts from the carry
+//                   of the column below (no carry adds, every multiply-add depends on the last)
+//   FE_COLS_TWO     two chains, 0 -> 1 -> 2 -> 3 and 4 -> 5 -> ... -> 9, their multiply-adds
+//                   interleaved; the carry 3 -> 4 -> 5 is added after the chains as fe_carry64
+//                   does.  Limb for limb the result fe_carry64 gives.
+//   FE_COLS_HALVES  two chains of five columns, 0 -> ... -> 4 and 5 -> ... -> 9, then 4 -> 5 -> 6
+//   FE_COLS_THREE   three chains, 0 -> 1 -> 2, 3 -> 4 -> 5 and 6 -> ... -> 9, then 2 -> 3 -> 4
+//                   and 5 -> 6 -> 7
+// Every form ends with the wrap 9 -> 0 -> 1 (times 19) in the carried limbs, and every form's
+// result is carried ("L", m <= 1.01); the one-chain form leaves limbs 0 and 2..9 below their
+// width and only limb 1 above it (by the wrap's last carry, < 2^17).
+// | FE_COLS_BYCOL: each column sum is one asm statement (mad_col) and the chains alternate column
+// by column; without it every multiply-add is a statement of its own and the chains alternate
+// term by term.
+enum { FE_COLS_PLAIN = 0, FE_COLS_SERIAL = 1, FE_COLS_TWO = 2, FE_COLS_HALVES = 3, FE_COLS_THREE = 4,
+       FE_COLS_BYCOL = 8 };
+// The kernels' form: one chain, a statement per column.  It has the fewest instructions (no carry
+// add is left) and was the fastest form of squaring and of multiply at every occupancy measured
+// (profiles/seeded_ubench_field_seeded.jsonl), one wave per SIMD included.
+#ifndef NWV_FE_FORM
+#define NWV_FE_FORM (FE_COLS_SERIAL | FE_COLS_BYCOL)
+#endif
+
+// term i of column k: the product a * b (false: the column has no such term).
+// Multiply: f_i g_j with i + j = k (mod 10), doubled when i and j are both odd (radix 2^25.5)
+// and multiplied by 19 when i + j >= 10 (2^255 = 19); f2 = odd limbs doubled, g19 = 19 g.
+// Squaring (55 products): pair (i < j) is doubled on f_i, the odd/odd doubling and the 19 of the
+// wrap go on f_j; diagonal terms carry the odd doubling and the wrap on one side.
+template <bool SQ>
+NWV_HD bool fe_term(const uint32_t* f, const uint32_t* f2, const uint32_t* g, const uint32_t* g19, int k, int i,
+                    uint32_t& a, uint32_t& b) {
+    const int j = (k - i + 10) % 10;
+    const bool wrap = (i + j) >= 10;
+    const bool dbl = (i & 1) && (j & 1);
+    if (SQ) {
+        if (j < i) return false;
+        a = (i == j) ? f[i] : (f[i] << 1);
+        b = f[j] * ((dbl ? 2u : 1u) * (wrap ? 19u : 1u));
+    } else {
+        a = dbl ? f2[i] : f[i];
+        b = wrap ? g19[j] : g[j];
+    }
+    return true;
+}
+
+// Column sums in one, two or three chains (chain c > 0 starts at column H2, H3; 0 = no such
+// chain), their multiply-adds interleaved term by term; each column after a chain's first is
+// seeded with the carry of the column below.  Then the carry of each chain's last column goes
+// into the next chain's (already carried) head and on into the column after it, and the wrap.
+// Every pre-carry sum, carry-in included, stays below 2^63 for inputs of magnitude <= 3.36.
+template <int H2, int H3, bool BYCOL, bool SQ>
+NWV_HD fe fe_cols_seeded(const uint32_t* f, const uint32_t* f2, const uint32_t* g, const uint32_t* g19) {
+    static_assert(H3 == 0 || (H2 > 0 && H3 >= H2 + 3 && H3 <= 8), "chain 1 carries its head's successor itself");
+    static_assert(H2 == 0 || H3 != 0 || H2 <= 8, "the last chain has two columns or more");
+    constexpr int NCH = H3 ? 3 : H2 ? 2 : 1;
+    constexpr int head[3] = {0, H2, H3};
+    constexpr int ncol[3] = {H2 ? H2 : 10, H2 ? (H3 ? H3 : 10) - H2 : 0, H3 ? 10 - H3 : 0};
+    constexpr int maxcol = ncol[0] > ncol[1] ? (ncol[0] > ncol[2] ? ncol[0] : ncol[2])
+                                             : (ncol[1] > ncol[2] ? ncol[1] : ncol[2]);
+    uint64_t acc[3] = {0, 0, 0}, sink[3] = {0, 0, 0};
+    uint32_t h[10];
+#pragma unroll
+    for (int cs = 0; cs < maxcol; cs++) {
+        if constexpr (BYCOL) {
+#pragma unroll
+            for (int c = 0; c < NCH; c++) {
+                const int nc = c == 0 ? ncol[0] : c == 1 ? ncol[1] : ncol[2];
+                if (cs >= nc) continue;
+                const int k = (c == 0 ? head[0] : c == 1 ? head[1] : head[2]) + cs;
+                uint32_t ta[10], tb[10];
+                int n = 0;
+#pragma unroll
+                for (int i = 0; i < 10; i++)
+                    if (fe_term<SQ>(f, f2, g, g19, k, i, ta[n], tb[n])) n++;
+                if (cs == 0) {
+                    acc[c] = mad_col(n - 1, ta + 1, tb + 1, (uint64_t)ta[0] * tb[0]);
+                } else {
+                    NWV_ASSERT(acc[c] < (1ull << 63));
+                    h[k - 1] = (uint32_t)acc[c] & ((k - 1) & 1 ? M25 : M26);
+                    acc[c] = mad_col(n, ta, tb, acc[c] >> limb_bits(k - 1));
+                }
+            }
+            continue;
+        }
+        bool started[3] = {false, false, false};
+#pragma unroll
+        for (int i = 0; i < 10; i++) {
+#pragma unroll
+            for (int c = 0; c < NCH; c++) {
+                const int nc = c == 0 ? ncol[0] : c == 1 ? ncol[1] : ncol[2];
+                if (cs >= nc) continue;
+                const int k = (c == 0 ? head[0] : c == 1 ? head[1] : head[2]) + cs;
+                uint32_t a, b;
+                if (!fe_term<SQ>(f, f2, g, g19, k, i, a, b)) continue;
+                if (!started[c]) {
+                    started[c] = true;
+                    if (cs == 0) {
+                        acc[c] = (uint64_t)a * b;
+                        continue;
+                    }
+                    NWV_ASSERT(acc[c] < (1ull << 63));
+                    h[k - 1] = (uint32_t)acc[c] & ((k - 1) & 1 ? M25 : M26);
+                    acc[c] >>= limb_bits(k - 1);
+                }
+                acc[c] = c == 0   ? mad_pin<0>(a, b, acc[c], sink[0])
+                         : c == 1 ? mad_pin<1>(a, b, acc[c], sink[1])
+                                  : mad_pin<2>(a, b, acc[c], sink[2]);
+            }
+        }
+    }
+#pragma unroll
+    for (int c = 1; c < NCH; c++) {
+        const int hd = c == 1 ? head[1] : head[2];
+        NWV_ASSERT(acc[c - 1] < (1ull << 63));
+        h[hd - 1] = (uint32_t)acc[c - 1] & ((hd - 1) & 1 ? M25 : M26);
+        const uint64_t t = h[hd] + (acc[c - 1] >> limb_bits(hd - 1));
+        h[hd] = (uint32_t)t & (hd & 1 ? M25 : M26);
+        h[hd + 1] += (uint32_t)(t >> limb_bits(hd));
+    }
+    NWV_ASSERT(acc[NCH - 1] < (1ull << 63));
+    h[9] = (uint32_t)acc[NCH - 1] & M25;
+    const uint64_t t0 = h[0] + (acc[NCH - 1] >> 25) * 19;
+    fe r;
+#pragma unroll
+    for (int i = 2; i < 10; i++) r.v[i] = h[i];
+    // last carry in 32 bits, as fe_carry64
+    r.v[0] = (uint32_t)t0 & M26;
+    r.v[1] = h[1] + (uint32_t)(t0 >> 26);
+    return r;
+}
+
+// the chains of a column-sum form: second and third head
+NWV_HD constexpr int fe_form_h2(int form) {
+    return (form & 7) == FE_COLS_TWO ? 4 : (form & 7) == FE_COLS_HALVES ? 5 : (form & 7) == FE_COLS_THREE ? 3 : 0;
+}
+NWV_HD constexpr int fe_form_h3(int form) { return (form & 7) == FE_COLS_THREE ? 6 : 0; }
+
+template <int FORM>
+NWV_HD fe fe_mul_form(const fe& f, const fe& g) {
     NWV_SEQ();
     NWV_COUNT(nwv_count_mul);
     fe_check(f, 3.36);
@@ -144,51 +352,66 @@ NWV_HD fe fe_mul(const fe& f, const fe& g) {
         g19[i] = g.v[i] * 19u;
         f2[i] = (i & 1) ? (f.v[i] << 1) : f.v[i];
     }
-    uint64_t h[10];
+    fe r;
+    if constexpr (FORM == FE_COLS_PLAIN) {
+        uint64_t h[10];
 #pragma unroll
-    for (int k = 0; k < 10; k++) {
-        uint64_t acc = 0;
+        for (int k = 0; k < 10; k++) {
+            uint64_t acc = 0;
 #pragma unroll
-        for (int i = 0; i < 10; i++) {
-            const int j = (k - i + 10) % 10;
-            const bool wrap = (i + j) >= 10;
-            const bool dbl = (i & 1) && (j & 1);
-            const uint32_t fa = dbl ? f2[i] : f.v[i];
-            const uint32_t gb = wrap ? g19[j] : g.v[j];
-            acc = mad(fa, gb, acc);
+            for (int i = 0; i < 10; i++) {
+                uint32_t a, b;
+                fe_term<false>(f.v, f2, g.v, g19, k, i, a, b);
+                acc = mad(a, b, acc);
+            }
+            NWV_ASSERT(acc < (1ull << 63));
+            h[k] = acc;
         }
-        h[k] = acc;
+        r = fe_carry64(h);
+    } else {
+        constexpr bool bycol = (FORM & FE_COLS_BYCOL) != 0;
+        r = fe_cols_seeded<fe_form_h2(FORM), fe_form_h3(FORM), bycol, false>(f.v, f2, g.v, g19);
     }
-    fe r = fe_carry64(h);
     NWV_SEQ();
     return r;
 }
 
-// h = f^2 (55 products): pair (i<j) is doubled on f_i, the odd/odd doubling and the 19 of
-// the wrap go on f_j; diagonal terms carry the odd doubling and the wrap on one side.
-NWV_HD fe fe_sq(const fe& f) {
+template <int FORM>
+NWV_HD fe fe_sq_form(const fe& f) {
     NWV_SEQ();
     NWV_COUNT(nwv_count_sq);
     fe_check(f, 3.36);
-    uint64_t h[10];
+    fe r;
+    if constexpr (FORM == FE_COLS_PLAIN) {
+        uint64_t h[10];
 #pragma unroll
-    for (int k = 0; k < 10; k++) h[k] = 0;
+        for (int k = 0; k < 10; k++) h[k] = 0;
 #pragma unroll
-    for (int i = 0; i < 10; i++) {
+        for (int i = 0; i < 10; i++) {
 #pragma unroll
-        for (int j = i; j < 10; j++) {
-            const int k = (i + j) % 10;
-            const bool wrap = (i + j) >= 10;
-            const bool dbl = (i & 1) && (j & 1);
-            uint32_t a = (i == j) ? f.v[i] : (f.v[i] << 1);
-            uint32_t b = f.v[j] * ((dbl ? 2u : 1u) * (wrap ? 19u : 1u));
-            h[k] = mad(a, b, h[k]);
+            for (int j = i; j < 10; j++) {
+                uint32_t a, b;
+                fe_term<true>(f.v, nullptr, nullptr, nullptr, (i + j) % 10, i, a, b);
+                h[(i + j) % 10] = mad(a, b, h[(i + j) % 10]);
+            }
         }
+#pragma unroll
+        for (int k = 0; k < 10; k++) NWV_ASSERT(h[k] < (1ull << 63));
+        r = fe_carry64(h);
+    } else {
+        constexpr bool bycol = (FORM & FE_COLS_BYCOL) != 0;
+        r = fe_cols_seeded<fe_form_h2(FORM), fe_form_h3(FORM), bycol, true>(f.v, nullptr, nullptr, nullptr);
     }
-    fe r = fe_carry64(h);
     NWV_SEQ();
     return r;
 }
+
+NWV_HD fe fe_mul(const fe& f, const fe& g) { return fe_mul_form<NWV_FE_FORM>(f, g); }
+NWV_HD fe fe_sq(const fe& f) { return fe_sq_form<NWV_FE_FORM>(f); }
+// f times a compile-time constant (fe_d, fe_d2, fe_sqrtm1): the plain form, in which the
+// constant's words and their multiples of 19 stay scalar operands; an asm statement's operands
+// are all VGPRs, twenty more live registers around such a product.
+NWV_HD fe fe_mul_const(const fe& f, const fe& c) { return fe_mul_form<FE_COLS_PLAIN>(f, c); }
 
 NWV_HD void fe_pin(fe& a);
 NWV_HD fe fe_sqn(fe f, int n) {
@@ -345,9 +568,9 @@ NWV_HD bool fe_sqrt_ratio_i(const fe& u_in, const fe& v_in, fe& r) {
     const bool correct = fe_is_zero(fe_sub(check, u));
     const bool flipped = fe_is_zero(fe_add(check, u));
     fe_pin(u);
-    const bool flipped_i = fe_is_zero(fe_add(check, fe_mul(u, fe_sqrtm1())));
+    const bool flipped_i = fe_is_zero(fe_add(check, fe_mul_const(u, fe_sqrtm1())));
     fe_pin(r);
-    fe r_prime = fe_mul(r, fe_sqrtm1());
+    fe r_prime = fe_mul_const(r, fe_sqrtm1());
     r = fe_select(r, r_prime, flipped || flipped_i);
     r = fe_select(r, fe_carry(fe_neg(r)), fe_is_negative(r) != 0);
     return correct || flipped;

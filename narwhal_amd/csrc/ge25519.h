@@ -149,7 +149,7 @@ NWV_HD void store_precomp_entry(uint32_t* e, const ge_precomp& c) {
 
 NWV_HD ge_cached ge_p3_to_cached(const ge_p3& p) {
     return ge_cached{fe_carry(fe_add(p.Y, p.X)), fe_carry(fe_sub(p.Y, p.X)),
-                     fe_carry(fe_add(p.Z, p.Z)), fe_mul(p.T, fe_d2())};
+                     fe_carry(fe_add(p.Z, p.Z)), fe_mul_const(p.T, fe_d2())};
 }
 // conditional negation of a cached point: -(x, y) = (-x, y): swap Y+X / Y-X, negate 2dT
 NWV_HD ge_cached ge_cached_cneg(const ge_cached& q, bool neg) {
@@ -177,7 +177,7 @@ NWV_HD void ge_uv_from_words(const uint32_t w[8], fe& y, fe& u, fe& v) {
     y = fe_from_words(w);
     fe yy = fe_sq(y);
     u = fe_carry(fe_sub(yy, fe_one()));
-    v = fe_carry(fe_add(fe_mul(yy, fe_d()), fe_one()));
+    v = fe_carry(fe_add(fe_mul_const(yy, fe_d()), fe_one()));
 }
 NWV_HD void words_pin(uint32_t w[8]) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -219,9 +219,9 @@ NWV_HD bool ge_decompress_post(const uint32_t w_in[8], fe pw, ge_p3& out) {
     const bool correct = fe_is_zero(fe_sub(check, u));
     const bool flipped = fe_is_zero(fe_add(check, u));
     fe_pin(u);
-    const bool flipped_i = fe_is_zero(fe_add(check, fe_mul(u, fe_sqrtm1())));
+    const bool flipped_i = fe_is_zero(fe_add(check, fe_mul_const(u, fe_sqrtm1())));
     fe_pin(r);
-    r = fe_select(r, fe_mul(r, fe_sqrtm1()), flipped || flipped_i);
+    r = fe_select(r, fe_mul_const(r, fe_sqrtm1()), flipped || flipped_i);
     r = fe_select(r, fe_carry(fe_neg(r)), fe_is_negative(r) != 0);
     // sign bit of the encoding; x = 0 with sign 1 ("negative zero") stays x = 0
     fe x = fe_select(r, fe_carry(fe_neg(r)), (w[7] >> 31) != 0);
@@ -246,7 +246,7 @@ NWV_HD ge_precomp ge_p3_to_precomp(const ge_p3& p) {
     fe x = fe_mul(p.X, zi);
     fe y = fe_mul(p.Y, zi);
     return ge_precomp{fe_carry(fe_add(y, x)), fe_carry(fe_sub(y, x)),
-                      fe_mul(fe_mul(x, y), fe_d2())};
+                      fe_mul_const(fe_mul(x, y), fe_d2())};
 }
 
 // identity test of a completed point: x = X/Z = 0 and y = Y/T = 1

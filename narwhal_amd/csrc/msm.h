@@ -355,7 +355,7 @@ static constexpr int COMB_WORDS = MSM_PT_WORDS * COMB_TABLES * COMB_ENTRIES;
 NWV_HD void msm_store_point(uint32_t* e, const ge_p3& p) {
     store_fe(e, fe_carry(fe_add(p.Y, p.X)));
     store_fe(e + 10, fe_carry(fe_sub(p.Y, p.X)));
-    store_fe(e + 20, fe_mul(p.T, fe_d2()));
+    store_fe(e + 20, fe_mul_const(p.T, fe_d2()));
     e[30] = 0u;
     e[31] = 0u;
 }

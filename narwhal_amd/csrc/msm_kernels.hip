@@ -1273,7 +1273,7 @@ __device__ __forceinline__ bool msm_tail_window(const MsmLayout& lay, const MsmT
     if (t < 4 * (m + 1)) {
         const ge_p3 pl = load_p3(lds + P3_WORDS * (t >> 2));
         const int c = t & 3;
-        fe v2 = c == 0 ? fe_add(pl.Y, pl.X) : c == 1 ? fe_sub(pl.Y, pl.X) : c == 2 ? fe_mul(pl.T, fe_d2())
+        fe v2 = c == 0 ? fe_add(pl.Y, pl.X) : c == 1 ? fe_sub(pl.Y, pl.X) : c == 2 ? fe_mul_const(pl.T, fe_d2())
                                                                                    : fe_add(pl.Z, pl.Z);
         fe_to_limbs16(fe_carry(v2), rows + 64 * (t >> 2) + 16 * c);
     }

@@ -11,8 +11,14 @@
 //                     compiler schedules by itself
 // Both reduce the 512-bit product by 2^256 = 38 (mod p) into 8 limbs < 2^32 (value < 2^256,
 // not canonical: the same lazy form the 10-limb code keeps).
-// Output: one JSON line per occupancy, plus {"check": ...} comparing every form's result of a
-// 64-squaring chain with the 10-limb result, canonically.
+// Column-sum forms of the 10-limb code (fe25519.h FE_COLS_*): the plain form (ten
+// independent sums, then fe_carry64's carry adds) against the forms that start each column sum
+// from the carry of the column below -- one serial chain, two chains (4 + 6 columns, 5 + 5) and
+// three, each with one asm statement per multiply-add (chains interleaved term by term) and with
+// one statement per column ("_bycol").
+// Output: one JSON line per occupancy for the radix comparison and one for the column-sum forms,
+// plus {"check": ...} comparing every radix form's result of a 64-squaring chain with the 10-limb
+// result, canonically, and {"check_forms": ...} comparing the column-sum forms with the plain one.
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include "../narwhal_amd/csrc/fe25519.h"
@@ -164,7 +170,7 @@ __device__ void fe8_freeze(const fe8& a, uint32_t w[8]) {
 
 enum { F10_SQ, F10_MUL, F8_SQ_PS, F8_SQ_OS, F8_MUL_PS };
 
-template <int OP, int ILP>
+template <int OP, int ILP, int FORM = FE_COLS_PLAIN>
 __global__ void __launch_bounds__(256) k_bench(uint32_t* out, int iters) {
     if constexpr (OP == F10_SQ || OP == F10_MUL) {
         fe f[ILP], g;
@@ -177,7 +183,7 @@ __global__ void __launch_bounds__(256) k_bench(uint32_t* out, int iters) {
 #pragma unroll
             for (int c = 0; c < ILP; c++) fe_pin(f[c]);
 #pragma unroll
-            for (int c = 0; c < ILP; c++) f[c] = OP == F10_SQ ? fe_sq(f[c]) : fe_mul(f[c], g);
+            for (int c = 0; c < ILP; c++) f[c] = OP == F10_SQ ? fe_sq_form<FORM>(f[c]) : fe_mul_form<FORM>(f[c], g);
         }
         uint32_t s = 0;
 #pragma unroll
@@ -222,11 +228,11 @@ __global__ void k_check(uint32_t* out) {
     for (int i = 0; i < 8; i++) a.v[i] = c.v[i] = w[i], b.v[i] = u[i];
     for (int r = 0; r < 8; r++) {
         for (int s = 0; s < 8; s++) {
-            f = fe_sq(f);
+            f = fe_sq_form<FE_COLS_PLAIN>(f);
             a = fe8_sq_ps(a);
             c = fe8_sq_os(c);
         }
-        f = fe_mul(f, g);
+        f = fe_mul_form<FE_COLS_PLAIN>(f, g);
         a = fe8_mul_ps(a, b);
         c = fe8_mul_ps(c, b);
     }
@@ -237,6 +243,48 @@ __global__ void k_check(uint32_t* out) {
     uint32_t bad = 0;
     for (int i = 0; i < 8; i++) bad |= (o10[i] != o8a[i]) | ((o10[i] != o8c[i]) << 1);
     atomicOr(out + 1, bad);
+}
+
+// the same chain in every column-sum form of the 10-limb code (fe25519.h FE_COLS_*): bit 0 of
+// out[2] = the serial form differs from the plain one canonically, bit 1 = the two-chain form
+// differs from the plain one in any limb (it promises fe_carry64's limbs), bits 2 and 3 = the
+// halves / three-chain form differs canonically, bit 4 = a by-column variant differs from its
+// term-by-term form in any limb
+template <int FORM>
+__device__ fe chain_form(fe f, const fe& g) {
+    for (int r = 0; r < 8; r++) {
+        for (int s = 0; s < 8; s++) f = fe_sq_form<FORM>(f);
+        f = fe_mul_form<FORM>(f, g);
+    }
+    return f;
+}
+__global__ void k_check_forms(uint32_t* out) {
+    const uint32_t t = threadIdx.x;
+    uint32_t w[8], u[8];
+    for (int i = 0; i < 8; i++) {
+        w[i] = (t + 1) * 0x9e3779b9u ^ (i * 0x7f4a7c15u);
+        u[i] = (t + 3) * 0x85ebca6bu ^ (i * 0xc2b2ae35u);
+    }
+    w[7] &= 0x7fffffffu;
+    u[7] &= 0x7fffffffu;
+    const fe f = fe_from_words(w), g = fe_from_words(u);
+    uint32_t bad = 0;
+    const fe p = chain_form<FE_COLS_PLAIN>(f, g), s = chain_form<FE_COLS_SERIAL>(f, g);
+    const fe d = chain_form<FE_COLS_TWO>(f, g), v = chain_form<FE_COLS_HALVES>(f, g);
+    const fe e = chain_form<FE_COLS_THREE>(f, g);
+    const fe sb = chain_form<FE_COLS_SERIAL | FE_COLS_BYCOL>(f, g), db = chain_form<FE_COLS_TWO | FE_COLS_BYCOL>(f, g);
+    const fe vb = chain_form<FE_COLS_HALVES | FE_COLS_BYCOL>(f, g), eb = chain_form<FE_COLS_THREE | FE_COLS_BYCOL>(f, g);
+    // the by-column variants give their term-by-term forms' limbs
+    for (int i = 0; i < 10; i++)
+        bad |= ((sb.v[i] != s.v[i]) | (db.v[i] != d.v[i]) | (vb.v[i] != v.v[i]) | (eb.v[i] != e.v[i])) << 4;
+    uint32_t op[8], os[8], ov[8], oe[8];
+    fe_freeze(p, op);
+    fe_freeze(s, os);
+    fe_freeze(v, ov);
+    fe_freeze(e, oe);
+    for (int i = 0; i < 8; i++) bad |= (op[i] != os[i]) | ((op[i] != ov[i]) << 2) | ((op[i] != oe[i]) << 3);
+    for (int i = 0; i < 10; i++) bad |= (p.v[i] != d.v[i]) << 1;
+    atomicOr(out + 2, bad);
 }
 
 template <class K>
@@ -261,6 +309,14 @@ double rate(K kern, uint32_t* out, int iters, int blocks, int ilp) {
     return (double)blocks * 256 * iters * ilp / (best * 1e-3);
 }
 
+template <int FORM>
+void forms_line(const char* name, uint32_t* out, int iters, int blocks, bool last) {
+    printf("\"%s\": {\"sq_ilp1\": %.4e, \"sq_ilp2\": %.4e, \"mul_ilp1\": %.4e, \"mul_ilp2\": %.4e}%s", name,
+           rate(k_bench<F10_SQ, 1, FORM>, out, iters, blocks, 1), rate(k_bench<F10_SQ, 2, FORM>, out, iters, blocks, 2),
+           rate(k_bench<F10_MUL, 1, FORM>, out, iters, blocks, 1),
+           rate(k_bench<F10_MUL, 2, FORM>, out, iters, blocks, 2), last ? "" : ", ");
+}
+
 int main() {
     uint32_t* out;
     hipMalloc(&out, 64);
@@ -271,6 +327,13 @@ int main() {
     printf("{\"check\": {\"sq8_ps_mul8_ps_equal_10limb\": %s, \"sq8_os_equal_10limb\": %s, \"lanes\": 256, "
            "\"chain\": \"8 x (8 squarings + 1 multiplication)\"}}\n",
            (h[1] & 1) ? "false" : "true", (h[1] & 2) ? "false" : "true");
+    hipLaunchKernelGGL(k_check_forms, dim3(1), dim3(256), 0, 0, out);
+    uint32_t hf = 31;
+    hipMemcpy(&hf, out + 2, 4, hipMemcpyDeviceToHost);
+    printf("{\"check_forms\": {\"serial_equal_plain\": %s, \"two_chains_same_limbs_as_plain\": %s, "
+           "\"halves_equal_plain\": %s, \"three_chains_equal_plain\": %s, \"bycol_same_limbs_as_term_by_term\": %s, \"lanes\": 256, \"chain\": \"8 x (8 squarings + 1 multiplication)\"}}\n",
+           (hf & 1) ? "false" : "true", (hf & 2) ? "false" : "true", (hf & 4) ? "false" : "true",
+           (hf & 8) ? "false" : "true", (hf & 16) ? "false" : "true");
     hipDeviceProp_t p;
     hipGetDeviceProperties(&p, 0);
     const int cus = p.multiProcessorCount;
@@ -285,6 +348,18 @@ int main() {
                rate(k_bench<F8_SQ_PS, 1>, out, iters, blocks, 1), rate(k_bench<F8_SQ_PS, 2>, out, iters, blocks, 2),
                rate(k_bench<F8_SQ_OS, 1>, out, iters, blocks, 1), rate(k_bench<F8_MUL_PS, 1>, out, iters, blocks, 1),
                rate(k_bench<F8_MUL_PS, 2>, out, iters, blocks, 2));
+        // the 10-limb code's column-sum forms (sq_ilp1 .. mul_ilp2 above are the plain form)
+        printf("{\"waves_per_simd\": %d, \"forms\": {", w);
+        forms_line<FE_COLS_PLAIN>("plain", out, iters, blocks, false);
+        forms_line<FE_COLS_SERIAL>("serial", out, iters, blocks, false);
+        forms_line<FE_COLS_TWO>("two_chains", out, iters, blocks, false);
+        forms_line<FE_COLS_HALVES>("halves", out, iters, blocks, false);
+        forms_line<FE_COLS_THREE>("three_chains", out, iters, blocks, false);
+        forms_line<FE_COLS_SERIAL | FE_COLS_BYCOL>("serial_bycol", out, iters, blocks, false);
+        forms_line<FE_COLS_TWO | FE_COLS_BYCOL>("two_chains_bycol", out, iters, blocks, false);
+        forms_line<FE_COLS_HALVES | FE_COLS_BYCOL>("halves_bycol", out, iters, blocks, false);
+        forms_line<FE_COLS_THREE | FE_COLS_BYCOL>("three_chains_bycol", out, iters, blocks, true);
+        printf("}}\n");
         fflush(stdout);
     }
     return 0;
