@@ -230,7 +230,10 @@ enum { FE_COLS_PLAIN = 0, FE_COLS_SERIAL = 1, FE_COLS_TWO = 2, FE_COLS_HALVES = 
 // Multiply: f_i g_j with i + j = k (mod 10), doubled when i and j are both odd (radix 2^25.5)
 // and multiplied by 19 when i + j >= 10 (2^255 = 19); f2 = odd limbs doubled, g19 = 19 g.
 // Squaring (55 products): pair (i < j) is doubled on f_i, the odd/odd doubling and the 19 of the
-// wrap go on f_j; diagonal terms carry the odd doubling and the wrap on one side.
+// wrap go on f_j; diagonal terms carry the odd doubling and the wrap on one side.  A wrapping
+// pair of an even i with j = 7 or 9 is f_i (38 f_j) instead of (2 f_i)(19 f_j): 38 f_7 and 38 f_9
+// exist for the odd/odd pairs and the diagonal, so 19 f_7, 19 f_9 and 2 f_8 are never formed
+// (13 scaled operands instead of 16); every product keeps its value.
 template <bool SQ>
 NWV_HD bool fe_term(const uint32_t* f, const uint32_t* f2, const uint32_t* g, const uint32_t* g19, int k, int i,
                     uint32_t& a, uint32_t& b) {
@@ -239,6 +242,11 @@ NWV_HD bool fe_term(const uint32_t* f, const uint32_t* f2, const uint32_t* g, co
     const bool dbl = (i & 1) && (j & 1);
     if (SQ) {
         if (j < i) return false;
+        if (wrap && !(i & 1) && (j == 7 || j == 9)) {
+            a = f[i];
+            b = f[j] * 38u;
+            return true;
+        }
         a = (i == j) ? f[i] : (f[i] << 1);
         b = f[j] * ((dbl ? 2u : 1u) * (wrap ? 19u : 1u));
     } else {
@@ -526,6 +534,12 @@ NWV_HD fe fe_pow_p58(const fe& x) {
 NWV_HD fe fe_d() {
     const uint32_t c[10] = {56195235, 13857412, 51736253, 6949390, 114729,
                             24766616, 60832955, 30306712, 48412415, 21499315};
+    fe r; for (int i = 0; i < 10; i++) r.v[i] = c[i]; return r;
+}
+// 1 / d: 2dxy of an affine Niels record times it is 2xy (msm_point_seed)
+NWV_HD fe fe_dinv() {
+    const uint32_t c[10] = {30013507, 3972531, 42321084, 12719050, 2979674,
+                            28954470, 51415654, 29910370, 18959708, 16925179};
     fe r; for (int i = 0; i < 10; i++) r.v[i] = c[i]; return r;
 }
 NWV_HD fe fe_d2() {

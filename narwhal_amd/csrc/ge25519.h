@@ -26,11 +26,14 @@ NWV_HD ge_cached ge_cached_identity() {
     return ge_cached{fe_one(), fe_one(), fe_small(2), fe_zero()};
 }
 
+// The products X T, Z Y, Z T, X Y: fe_mul(f, g) scales g by 19 and doubles the odd limbs of f, and
+// with X and Z always on the left, T and Y always on the right, only two operands of each kind
+// are prepared (Y Z in the other order needs 19 Z and the doubled Y as well).
 NWV_HD ge_p3 ge_p1p1_to_p3(const ge_p1p1& c) {
-    return ge_p3{fe_mul(c.X, c.T), fe_mul(c.Y, c.Z), fe_mul(c.Z, c.T), fe_mul(c.X, c.Y)};
+    return ge_p3{fe_mul(c.X, c.T), fe_mul(c.Z, c.Y), fe_mul(c.Z, c.T), fe_mul(c.X, c.Y)};
 }
 NWV_HD ge_p2 ge_p1p1_to_p2(const ge_p1p1& c) {
-    return ge_p2{fe_mul(c.X, c.T), fe_mul(c.Y, c.Z), fe_mul(c.Z, c.T)};
+    return ge_p2{fe_mul(c.X, c.T), fe_mul(c.Z, c.Y), fe_mul(c.Z, c.T)};
 }
 NWV_HD ge_p2 ge_p3_to_p2(const ge_p3& p) { return ge_p2{p.X, p.Y, p.Z}; }
 

@@ -369,6 +369,13 @@ NWV_HD ge_precomp msm_point_select(const fe& ypx, const fe& ymx, const fe& xy2d,
     const fe nxy = fe_neg(xy2d);  // 2p - 2dxy: limbs < 2^27, a valid multiply input
     return ge_precomp{fe_select(ypx, ymx, neg), fe_select(ymx, ypx, neg), fe_select(xy2d, nxy, neg)};
 }
+// The point of a (sign-selected) record as a running sum, without adding it to the identity:
+// (2x : 2y : 2 : 2xy) = (ypx - ymx : ypx + ymx : 2 : xy2d / d), one constant multiply instead of
+// the seven of a mixed addition.  X and Y are carried (the next addition adds and subtracts them).
+NWV_HD ge_p3 msm_point_seed(const ge_precomp& q) {
+    return ge_p3{fe_carry(fe_sub(q.ypx, q.ymx)), fe_carry(fe_add(q.ypx, q.ymx)), fe_small(2),
+                 fe_mul_const(q.xy2d, fe_dinv())};
+}
 NWV_HD ge_precomp msm_load_point(const uint32_t* e, bool neg) {
     return msm_point_select(load_fe(e), load_fe(e + 10), load_fe(e + 20), neg);
 }

@@ -22,6 +22,8 @@
 // the (rare) failure flags.  Entry order inside a bucket depends on LDS atomic order, which
 // changes the projective representation of a bucket sum but never the group element, so the
 // verdict is deterministic.
+#include <type_traits>
+
 #include "fe_row.h"
 #include "msm.h"
 
@@ -821,10 +823,14 @@ extern "C" __global__ void __launch_bounds__(256) k_msm_bucket(
     const uint32_t klim = nkeys - 1;
     auto next_end = [&]() { return kstart[key + 2 < klim ? key + 2 : klim]; };
     uint32_t pf_val = next_end();
-    // add entry k (record w, index word v); close the key segment when it ends here
+    // add entry k (record w, index word v); close the key segment when it ends here.  The chunk's
+    // first entry (seed: the same step in every live lane of the wave) becomes the sum as it is
+    // instead of being added to the identity; after a close inside the chunk the sum restarts
+    // from the identity, since only some lanes close there and a select would cost all of them
     const uint32_t zero = 0u - (T >> 31);  // T < 2^31: all-zero, opaque to the compiler
-    auto step = [&](const uint32_t* w, uint32_t v, uint32_t k) {
-        acc = ge_p1p1_to_p3(ge_madd(acc, msm_point_of(w, v, zero)));
+    auto step = [&](const uint32_t* w, uint32_t v, uint32_t k, auto seed) {
+        if constexpr (decltype(seed)::value) acc = msm_point_seed(msm_point_of(w, v, zero));
+        else acc = ge_p1p1_to_p3(ge_madd(acc, msm_point_of(w, v, zero)));
         if (k + 1 == k1 || k + 1 == kend) {
             store_p3(head ? hpart + (size_t)P3_WORDS * (k0 / T) : bsum + (size_t)P3_WORDS * key, acc);
             acc = ge_p3_identity();
@@ -850,25 +856,31 @@ extern "C" __global__ void __launch_bounds__(256) k_msm_bucket(
     const uint32_t klast = k1 - 1;
     auto at = [&](uint32_t k) { return entries[k < klast ? k : klast]; };
     uint32_t wa[32], wb[32];
-    uint32_t va = entries[k0];
+    const uint32_t v0 = entries[k0];
     uint32_t vb = at((uint32_t)k0 + 1);
-    msm_load_raw(pts, va, wa);
+    msm_load_raw(pts, v0, wa);
+    // index loads go out before the record loads: the memory counter is in order, so a
+    // wait for an index never waits for a record still in flight
+    uint32_t va = at((uint32_t)k0 + 2);
+    msm_load_raw(pts, vb, wb);
+    step(wa, v0, (uint32_t)k0, std::true_type{});
+    pf_val = next_end();
+    if (k0 + 1 >= k1) return;
+    // entry k is in wb (index word vb), va is the index word of entry k + 1
 #pragma unroll 1
-    for (uint32_t k = (uint32_t)k0;; k += 2) {
-        // index loads go out before the record loads: the memory counter is in order, so a
-        // wait for an index never waits for a record still in flight
+    for (uint32_t k = (uint32_t)k0 + 1;; k += 2) {
         const uint32_t vc = at(k + 2);
-        msm_load_raw(pts, vb, wb);
-        step(wa, va, k);
+        msm_load_raw(pts, va, wa);
+        step(wb, vb, k, std::false_type{});
         pf_val = next_end();
         if (k + 1 >= k1) break;
         const uint32_t vd = at(k + 3);
-        msm_load_raw(pts, vc, wa);
-        step(wb, vb, k + 1);
+        msm_load_raw(pts, vc, wb);
+        step(wa, va, k + 1, std::false_type{});
         pf_val = next_end();
         if (k + 2 >= k1) break;
-        va = vc;
-        vb = vd;
+        vb = vc;
+        va = vd;
     }
 }
 

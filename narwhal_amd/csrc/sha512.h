@@ -119,13 +119,25 @@ NWV_HD uint64_t rotr64(uint64_t x, int n) {
     const u64p r = rotr(u64p{lo, hi}, n);
     return ((uint64_t)r.hi << 32) | r.lo;
 }
+// (hi : lo) as one 64-bit addend the optimiser cannot take apart again.  Left visible, the
+// disjoint `|` of the join becomes an add, and the sums it enters are reassociated into
+// h + (hi << 32) + zext(lo): two or three extra v_lshl_add_u64 a round, and v_mov to build the
+// zero-extended pairs.  The empty statement costs no instruction: the halves are written
+// straight into the register pair.
+NWV_HD uint64_t join64(uint32_t lo, uint32_t hi) {
+    uint64_t r = ((uint64_t)hi << 32) | lo;
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm("" : "+v"(r));
+#endif
+    return r;
+}
 NWV_HD uint64_t xor3_64(uint64_t a, uint64_t b, uint64_t c) {
-    return ((uint64_t)xor3_32((uint32_t)(a >> 32), (uint32_t)(b >> 32), (uint32_t)(c >> 32)) << 32) |
-           xor3_32((uint32_t)a, (uint32_t)b, (uint32_t)c);
+    return join64(xor3_32((uint32_t)a, (uint32_t)b, (uint32_t)c),
+                  xor3_32((uint32_t)(a >> 32), (uint32_t)(b >> 32), (uint32_t)(c >> 32)));
 }
 NWV_HD uint64_t bitop3_64(uint64_t a, uint64_t b, uint64_t c, int tt) {
-    return ((uint64_t)bitop3_32((uint32_t)(a >> 32), (uint32_t)(b >> 32), (uint32_t)(c >> 32), tt) << 32) |
-           bitop3_32((uint32_t)a, (uint32_t)b, (uint32_t)c, tt);
+    return join64(bitop3_32((uint32_t)a, (uint32_t)b, (uint32_t)c, tt),
+                  bitop3_32((uint32_t)(a >> 32), (uint32_t)(b >> 32), (uint32_t)(c >> 32), tt));
 }
 NWV_HD uint64_t j64(u64p x) { return ((uint64_t)x.hi << 32) | x.lo; }
 #define NWV_SHA_ROUND(r, wr)                                                                   \
