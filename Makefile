@@ -38,7 +38,7 @@ oracle:
 	$(MAKE) -C oracle
 
 hostemu: tests/_build/libhostemu.so tests/_build/libsvcstub.so tests/_build/libblsemu.so tests/_build/libblsshard.so \
-	tests/_build/libcombemu.so tests/_build/libfeseeded.so tests/_build/libtrimemu.so
+	tests/_build/libcombemu.so tests/_build/libfeseeded.so tests/_build/libtrimemu.so tests/_build/libfoldemu.so
 # the BLS and Ed25519 calls' split over a multi-device context (bls_shard.h, shard.h) with stub per-device work
 tests/_build/libblsshard.so: tests/hostemu/bls_shard_stub.cpp narwhal_amd/csrc/bls_shard.h narwhal_amd/csrc/shard.h
 	@mkdir -p tests/_build
@@ -76,6 +76,11 @@ tests/_build/libfeseeded.so: tests/hostemu/fe_seeded_hostemu.cpp narwhal_amd/csr
 tests/_build/libtrimemu.so: tests/hostemu/trim_hostemu.cpp $(CSRC)
 	@mkdir -p tests/_build
 	$(HIPCC) -std=c++17 -O1 --offload-host-only -x hip -DNWV_BOUNDS_CHECK -fPIC -shared -o $@ tests/hostemu/trim_hostemu.cpp
+# the reduction mod l by folding, the unreduced sums of z s, the in-order digit recoding and the
+# decompression with its stash on the host (tests/test_fold_hostemu.py)
+tests/_build/libfoldemu.so: tests/hostemu/fold_hostemu.cpp $(CSRC)
+	@mkdir -p tests/_build
+	$(HIPCC) -std=c++17 -O1 --offload-host-only -x hip -DNWV_BOUNDS_CHECK -fPIC -shared -o $@ tests/hostemu/fold_hostemu.cpp
 
 tools: tools/ubench_valu tools/ubench_field tools/ubench_wave tools/ubench_row tools/ubench_prep tools/libsvcbench.so \
 	tools/fe_vectors

@@ -45,9 +45,9 @@ NWV_HD int take_top_digit(uint32_t y[8], int w) {
     return d;
 }
 
-// k = SHA-512(R || A || M) mod l
-NWV_HD void challenge_scalar(const uint32_t Rw[8], const uint32_t Aw[8], const uint8_t* msg,
-                             uint32_t mlen, uint32_t k[8]) {
+// hw = SHA-512(R || A || M), as the 512-bit little-endian integer that k is the residue of
+NWV_HD void challenge_hash_words(const uint32_t Rw[8], const uint32_t Aw[8], const uint8_t* msg,
+                                 uint32_t mlen, uint32_t hw[16]) {
     uint32_t pre[16];
 #pragma unroll
     for (int i = 0; i < 8; i++) {
@@ -56,8 +56,13 @@ NWV_HD void challenge_scalar(const uint32_t Rw[8], const uint32_t Aw[8], const u
     }
     sha512_state st;
     sha512_prefixed_msg(st, pre, msg, mlen);
-    uint32_t hw[16];
     sha512_digest_words(st, hw);
+}
+// k = SHA-512(R || A || M) mod l
+NWV_HD void challenge_scalar(const uint32_t Rw[8], const uint32_t Aw[8], const uint8_t* msg,
+                             uint32_t mlen, uint32_t k[8]) {
+    uint32_t hw[16];
+    challenge_hash_words(Rw, Aw, msg, mlen, hw);
     sc_reduce512(hw, k);
 }
 

@@ -202,6 +202,8 @@ NWV_HD fe ge_decompress_pre(const uint32_t w[8]) {
     return fe_mul(u, fe_mul(fe_sq(v3), v));
 }
 NWV_HD bool ge_decompress_post(const uint32_t w_in[8], fe pw, ge_p3& out);
+NWV_HD bool ge_decompress_finish(const uint32_t w[8], const fe& y, fe u, const fe& v, const fe& uv3, const fe& pw,
+                                 ge_p3& out);
 NWV_HD bool ge_decompress(const uint32_t w_in[8], ge_p3& out) {
     uint32_t w[8];
 #pragma unroll
@@ -217,7 +219,12 @@ NWV_HD bool ge_decompress_post(const uint32_t w_in[8], fe pw, ge_p3& out) {
     words_pin(w);
     fe y, u, v;
     ge_uv_from_words(w, y, u, v);
-    fe r = fe_mul(fe_mul(u, fe_mul(fe_sq(v), v)), pw);  // (u v^3)(u v^7)^((p-5)/8)
+    return ge_decompress_finish(w, y, u, v, fe_mul(u, fe_mul(fe_sq(v), v)), pw, out);
+}
+// the root, its test and the sign from u, v, u v^3 and the power (w: the encoding, for its sign bit)
+NWV_HD bool ge_decompress_finish(const uint32_t w[8], const fe& y, fe u, const fe& v, const fe& uv3, const fe& pw,
+                                 ge_p3& out) {
+    fe r = fe_mul(uv3, pw);  // (u v^3)(u v^7)^((p-5)/8)
     fe check = fe_carry(fe_mul(v, fe_sq(r)));
     const bool correct = fe_is_zero(fe_sub(check, u));
     const bool flipped = fe_is_zero(fe_add(check, u));
@@ -233,6 +240,43 @@ NWV_HD bool ge_decompress_post(const uint32_t w_in[8], fe pw, ge_p3& out) {
     out.Z = fe_one();
     out.T = fe_mul(x, y);
     return correct || flipped;
+}
+
+// ge_decompress with u, v and u v^3 parked in a stash across the power instead of recomputed after
+// it (two squarings, two multiplies, the multiply by d): the batch MSM's lane-local decompression,
+// whose stash is LDS -- 30 words a lane, word k at sh[k STRIDE] (STRIDE = the workgroup's lanes:
+// consecutive lanes in consecutive banks, every offset an immediate).  The prelude forms u v^7 as
+// (u v^3) (v^2)^2: two squarings and three multiplies as in ge_decompress_pre, with u v^3 on the
+// way.  y is two shifts a limb from the encoding, which stays live for its sign bit anyway.
+template <int STRIDE>
+NWV_HD bool ge_decompress_stash(const uint32_t w_in[8], uint32_t* sh, ge_p3& out) {
+    uint32_t w[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) w[i] = w_in[i];
+    fe pw;
+    {
+        fe y, u, v;
+        ge_uv_from_words(w, y, u, v);
+        const fe v2 = fe_sq(v);
+        const fe uv3 = fe_mul(u, fe_mul(v2, v));
+#pragma unroll
+        for (int k = 0; k < 10; k++) {
+            sh[k * STRIDE] = u.v[k];
+            sh[(10 + k) * STRIDE] = v.v[k];
+            sh[(20 + k) * STRIDE] = uv3.v[k];
+        }
+        pw = fe_pow_p58(fe_mul(uv3, fe_sq(v2)));
+    }
+    fe_pin(pw);
+    words_pin(w);
+    fe u, v, uv3;
+#pragma unroll
+    for (int k = 0; k < 10; k++) {
+        u.v[k] = sh[k * STRIDE];
+        v.v[k] = sh[(10 + k) * STRIDE];
+        uv3.v[k] = sh[(20 + k) * STRIDE];
+    }
+    return ge_decompress_finish(w, fe_from_words(w), u, v, uv3, pw, out);
 }
 
 // affine (x, y) -> compressed words (y with the sign of x in bit 255)

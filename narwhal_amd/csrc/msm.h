@@ -295,6 +295,42 @@ NWV_HD void msm_xcd_map(const MsmLayout& L, uint64_t n, uint64_t na, uint32_t ch
 }
 static_assert(MSM_MAX_WINDOWS <= MSM_XCD_GROUPS * MSM_XCD_WIN, "every window needs a group slot");
 
+// sum of z_i s_i: a hash lane's product z_i s_i stays an unreduced integer (z < 2^128, s < 2^256:
+// 12 words); a hash workgroup of up to 256 lanes hands k_msm_tail their sum (< 2^392: 13 words),
+// and the sum over a batch's workgroups (fewer than 2^16) stays below 2^408, reduced mod l once.
+static constexpr int MSM_ZS_WORDS = 12, MSM_PARTIAL_WORDS = 13;
+// a workgroup's column sums (word k of its lanes' products, each sum < 2^40) -> its 13-word partial
+NWV_HD void msm_zs_partial(const unsigned long long col[MSM_ZS_WORDS], uint32_t out[MSM_PARTIAL_WORDS]) {
+    unsigned long long c = 0;
+    for (int k = 0; k < MSM_ZS_WORDS; k++) {
+        c += col[k];
+        out[k] = (uint32_t)c;
+        c >>= 32;
+    }
+    out[MSM_ZS_WORDS] = (uint32_t)c;
+}
+// the column sums of a batch's partials (fewer than 2^16 of them: each sum < 2^48) -> sum of
+// z_i s_i mod l
+NWV_HD void msm_zs_total(const unsigned long long col[MSM_PARTIAL_WORDS], uint32_t r[8]) {
+    uint32_t x[16];
+    unsigned long long c = 0;
+    for (int k = 0; k < 16; k++) {
+        if (k < MSM_PARTIAL_WORDS) c += col[k];
+        x[k] = (uint32_t)c;
+        c >>= 32;
+    }
+    sc_reduce512(x, r);
+}
+// k_msm_prep's dynamic LDS, one area shared by its roles (a workgroup runs one role only): the hash
+// role's nt rows of z_i s_i (MSM_ZS_WORDS + 1 words apart), the lane-local decompression's u, v and
+// u v^3 (MSM_STASH_WORDS words a lane, word-major; the row form keeps its own static rows)
+static constexpr int MSM_STASH_WORDS = 30;
+static constexpr int MSM_PREP_THREADS = 256;  // the lane-local form's workgroup (the stash's stride)
+NWV_HD uint32_t msm_prep_lds_bytes(uint32_t nt, bool rows) {
+    const uint32_t hash = nt * (MSM_ZS_WORDS + 1), dec = rows ? 0u : nt * MSM_STASH_WORDS;
+    return 4u * (hash > dec ? hash : dec);
+}
+
 // raw bits [pos, pos + width) of a 256-bit little-endian scalar (width <= 16)
 NWV_HD uint32_t msm_window_bits(const uint32_t s[8], int pos, int width) {
     uint64_t v = 0;
@@ -322,6 +358,33 @@ NWV_HD void msm_recode(const uint32_t s[8], const MsmLayout& L, int nw, Emit emi
             carry = 1;
         }
         emit(w, d);
+    }
+}
+
+// msm_recode for the hash lanes, writing straight into the digit rows: digit w goes to col[w * np]
+// (col = the point's column in row 0).  The windows ascend and their positions are wave-uniform,
+// so the words are walked in order: for each word k the windows that start in it take their bits
+// from the pair (s[k], s[k+1]) held in two fixed registers -- no selection of a word by a computed
+// index -- and the row pointer steps by np.  Same digits and carry rule as msm_recode.
+NWV_HD void msm_recode_rows(const uint32_t s[8], const MsmLayout& L, int nw, int16_t* col, uint64_t np) {
+    uint32_t carry = 0;
+    int w = 0;
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        const uint64_t pair = (uint64_t)s[k] | (k < 7 ? (uint64_t)s[k + 1] << 32 : 0ull);
+#pragma unroll 1
+        while (w < nw && (L.pos[w] >> 5) == k) {
+            const int c = L.width[w];
+            int d = (int)(((uint32_t)(pair >> (L.pos[w] & 31)) & ((1u << c) - 1u)) + carry);
+            carry = 0;
+            if (w + 1 < nw && d >= (1 << (c - 1))) {
+                d -= 1 << c;
+                carry = 1;
+            }
+            *col = (int16_t)d;
+            col += np;
+            w++;
+        }
     }
 }
 

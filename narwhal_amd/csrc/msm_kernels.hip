@@ -29,6 +29,9 @@
 
 using namespace nwv;
 
+// k_msm_scalars / k_msm_points / k_msm_prep's dynamic LDS: msm_prep_lds_bytes (msm.h) at launch
+extern __shared__ uint32_t prep_lds[];
+
 namespace {
 
 __device__ __forceinline__ void msm_load8(const uint8_t* p, uint32_t w[8]) {
@@ -71,8 +74,8 @@ __device__ __forceinline__ ge_p3 shfl_down_p3(const ge_p3& p, int o) {
 }  // namespace
 
 // digits: [window][na+1+n] signed digits of every point's scalar (A points at [0, na), B's
-// entry na written by k_msm_bscalar, R_i at na+1+i); partial: gridDim.x x 9 words (sum of z_i s_i over the workgroup, as a
-// plain 288-bit integer); fail: bit 0 set when any s_i >= l
+// entry na written by k_msm_bscalar, R_i at na+1+i); partial: gridDim.x x 13 words (sum of the unreduced
+// products z_i s_i over the workgroup, as a plain 416-bit integer); fail: bit 0 set when any s_i >= l
 struct MsmScalarArgs {
     uint64_t n, na;
     int keyed;
@@ -168,16 +171,22 @@ __device__ __forceinline__ void msm_scalars_block(uint32_t blk, const MsmScalarA
     int16_t* __restrict__ digits = g.digits;
     uint32_t* __restrict__ fail = g.fail;
     const int keyed = g.keyed;
-    __shared__ uint32_t zs_lds[256 * 9];
+    uint32_t* zs_lds = prep_lds;  // nt x MSM_ZS_WORDS + 1 words
     const uint32_t nt = blockDim.x;  // 256, or 64 when the call's decompression runs on rows
     const uint64_t i = (uint64_t)blk * nt + threadIdx.x;
-    uint32_t zs[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    // z_i s_i as a plain integer (z < 2^128, s < 2^256): reduced once per batch, by msm_bterm
+    uint32_t zs[MSM_ZS_WORDS] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     if (i < n) {
         uint32_t Aw[8], Rw[8], Sw[8], k[8], z[8], a[8];
         msm_load8(pk + 32 * i, Aw);
         msm_load8(sig + 64 * i, Rw);
         msm_load8(sig + 64 * i + 32, Sw);
-        const uint32_t f = lane_hash(Aw, Rw, Sw, msg + g.msg_off[i], g.msg_len[i], k);
+        {
+            uint32_t hw[16];
+            challenge_hash_words(Rw, Aw, msg + g.msg_off[i], g.msg_len[i], hw);
+            sc_reduce512_fold(hw, k);
+        }
+        const uint32_t f = sc_is_canonical(Sw) ? FLAG_S_OK : 0u;
         if (f != FLAG_S_OK) atomicOr(fail, 1u);
         if (g.kout) {
             msm_store8(g.kout + 8 * i, k);
@@ -188,37 +197,33 @@ __device__ __forceinline__ void msm_scalars_block(uint32_t blk, const MsmScalarA
 #pragma unroll
         for (int k = 0; k < 8; k++) sd[k] = seedp[k];
         msm_z(sd, i, z);
-        sc_mul(z, k, a);
-        sc_mul(z, Sw, zs);
+        {
+            uint32_t zk[12];  // z has four words: 4 x 8 products, a = z k < 2^381 folded to < l
+            sc_mul_4x8(z, k, zk);
+            sc_reduce384_fold(zk, a);
+        }
+        sc_mul_4x8(z, Sw, zs);
         // signed digits straight from registers (window-major rows): R_i always; A_i's scalar
         // z_i k_i here when every signature has its own A point, else summed per key by
         // k_msm_keysum first
         const uint64_t np = na + 1 + n;
         if (keyed) msm_store8(g.ascal + 8 * i, a);
-        else msm_recode(a, lay, lay.nw, [&](int w, int d) { digits[(uint64_t)w * np + i] = (int16_t)d; });
-        msm_recode(z, lay, lay.nw_z, [&](int w, int d) { digits[(uint64_t)w * np + na + 1 + i] = (int16_t)d; });
+        else msm_recode_rows(a, lay, lay.nw, digits + i, np);
+        msm_recode_rows(z, lay, lay.nw_z, digits + na + 1 + i, np);
     }
 #pragma unroll
-    for (int k = 0; k < 8; k++) zs_lds[threadIdx.x * 9 + k] = zs[k];
+    for (int k = 0; k < MSM_ZS_WORDS; k++) zs_lds[threadIdx.x * (MSM_ZS_WORDS + 1) + k] = zs[k];
     __syncthreads();
-    // column sums: thread t < 8 adds word t of the nt values (< 2^40), then thread 0 carries
-    __shared__ unsigned long long col[8];
-    if (threadIdx.x < 8) {
+    // column sums: thread t < 12 adds word t of the nt values (< 2^40), then thread 0 carries:
+    // the workgroup's sum < 2^392 as 13 words
+    __shared__ unsigned long long col[MSM_ZS_WORDS];
+    if (threadIdx.x < MSM_ZS_WORDS) {
         unsigned long long s = 0;
-        for (uint32_t r = 0; r < nt; r++) s += zs_lds[r * 9 + threadIdx.x];
+        for (uint32_t r = 0; r < nt; r++) s += zs_lds[r * (MSM_ZS_WORDS + 1) + threadIdx.x];
         col[threadIdx.x] = s;
     }
     __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long c = 0;
-        uint32_t* out = g.partial + 9 * blk;
-        for (int k = 0; k < 8; k++) {
-            c += col[k];
-            out[k] = (uint32_t)c;
-            c >>= 32;
-        }
-        out[8] = (uint32_t)c;
-    }
+    if (threadIdx.x == 0) msm_zs_partial(col, g.partial + MSM_PARTIAL_WORDS * blk);
     if (blk == 0 && threadIdx.x < (unsigned)lay.nw) {  // B's digit column(s) stay empty
         const uint64_t np = na + 1 + n;
         digits[(uint64_t)threadIdx.x * np + na] = 0;
@@ -335,7 +340,9 @@ __device__ __forceinline__ void msm_points_block(uint32_t blk, const MsmPointArg
     uint32_t w[8];
     msm_load8(is_r ? g.sig + 64 * i : g.apk + 32 * i, w);
     ge_p3 P;
-    const bool ok = ge_decompress(w, P);
+    // u, v and u v^3 wait in the workgroup's LDS area through the power (the host launches this
+    // form with MSM_PREP_THREADS threads: word k of lane t at prep_lds[k MSM_PREP_THREADS + t])
+    const bool ok = ge_decompress_stash<MSM_PREP_THREADS>(w, prep_lds + threadIdx.x, P);
     uint32_t* e = g.pts + (size_t)MSM_PT_WORDS * (is_r ? na + 1 + i : i);
     msm_store_point(e, P);
     e[MSM_PT_WORDS - 1] = ok ? 0u : 1u;  // decode flag (k_ed_points_msm); ignored by the MSM
@@ -992,7 +999,7 @@ struct MsmTailArgs {
                            // in cached row form (the final sum's terms)
     uint32_t* ctr;         // [0, nw): chunk arrivals; [64, 64 + nw): window w's term published
     const uint32_t* fail;
-    const uint32_t* partial;   // k_msm_prep's per-workgroup sums of z_i s_i (nblk x 9 words)
+    const uint32_t* partial;   // k_msm_prep's per-workgroup sums of z_i s_i (nblk x 13 words)
     const uint32_t* comb;      // fixed-base comb table
     uint32_t nblk;
     uint32_t quad_max_c;  // chunk butterflies of at most this many buckets run on quads (0: never)
@@ -1074,15 +1081,16 @@ __device__ __forceinline__ bool tail_arrive(uint32_t* ctr, uint32_t expect, uint
 // additions) -> acc0 (64 words of LDS: row limbs, the final sum's first term), in wave 0.
 __device__ __forceinline__ void msm_bterm(const uint32_t* __restrict__ partial, uint32_t nblk,
                                           const uint32_t* __restrict__ comb, uint32_t* __restrict__ acc0) {
-    __shared__ unsigned long long wcol[4][9];
+    __shared__ unsigned long long wcol[4][MSM_PARTIAL_WORDS];
     __shared__ int dig[COMB_TABLES];
     const int t = threadIdx.x, wid = t >> 6, lane = t & 63;
-    unsigned long long s[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    unsigned long long s[MSM_PARTIAL_WORDS] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     for (uint32_t q = t; q < nblk; q += 256)
 #pragma unroll
-        for (int k = 0; k < 9; k++) s[k] += partial[9 * (size_t)q + k];  // < 2^32 each, < 2^16 of them
+        for (int k = 0; k < MSM_PARTIAL_WORDS; k++)
+            s[k] += partial[MSM_PARTIAL_WORDS * (size_t)q + k];  // < 2^32 each, < 2^16 of them
 #pragma unroll
-    for (int k = 0; k < 9; k++) {
+    for (int k = 0; k < MSM_PARTIAL_WORDS; k++) {
         unsigned long long v = s[k];
 #pragma unroll
         for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -1090,15 +1098,11 @@ __device__ __forceinline__ void msm_bterm(const uint32_t* __restrict__ partial, 
     }
     __syncthreads();
     if (t == 0) {
-        uint32_t x[16];
-        unsigned long long c = 0;
-        for (int k = 0; k < 16; k++) {
-            if (k < 9) c += wcol[0][k] + wcol[1][k] + wcol[2][k] + wcol[3][k];
-            x[k] = (uint32_t)c;
-            c >>= 32;
-        }
+        // the partials are unreduced integers < 2^392 each: their sum < 2^408, reduced here once
+        unsigned long long cs[MSM_PARTIAL_WORDS];
+        for (int k = 0; k < MSM_PARTIAL_WORDS; k++) cs[k] = wcol[0][k] + wcol[1][k] + wcol[2][k] + wcol[3][k];
         uint32_t r[8], b[8], c8[8];
-        sc_reduce512(x, r);
+        msm_zs_total(cs, r);
         uint32_t nz = 0;
         for (int k = 0; k < 8; k++) nz |= r[k];
         long long br = 0;

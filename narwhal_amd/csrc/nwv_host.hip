@@ -601,7 +601,7 @@ constexpr size_t MSM_CTR_BYTES = 512;  // k_msm_tail arrival counters (128 words
 int msm_alloc(EdBuffers& b, const MsmPlan& p, size_t n) {
     const size_t nblk = (n + 63) / 64;  // k_msm_prep's hash workgroups (64 or 256 threads)
     int rc;
-    if ((b.nkeys_distinct && (rc = b.m_ascal.ensure(32 * n + 32))) || (rc = b.m_partial.ensure(36 * nblk + 36)) ||
+    if ((b.nkeys_distinct && (rc = b.m_ascal.ensure(32 * n + 32))) || (rc = b.m_partial.ensure(4 * MSM_PARTIAL_WORDS * (nblk + 1))) ||
         (rc = b.m_state.ensure(128)) ||
         (rc = b.m_pts.ensure((size_t)4 * MSM_PT_WORDS * p.np + 64)) ||
         (rc = b.m_digits.ensure((size_t)2 * p.lay.nw * p.np + 64)) ||
@@ -685,7 +685,8 @@ int msm_launch(Lane& d, EdBuffers& b, size_t n, const uint8_t seed32[32], hipStr
                           b.sig.as<uint8_t>(), b.m_pts.as<uint32_t>(), state, rows ? 1u : 0u};
     // row form: single-wave workgroups (a wave alone on its CU decompresses faster than four
     // waves of one workgroup sharing a CU), so the fused grid's hash role uses 64 threads too
-    const unsigned pthr = rows ? 64u : 256u;
+    const unsigned pthr = rows ? 64u : (unsigned)MSM_PREP_THREADS;
+    const unsigned plds = msm_prep_lds_bytes(pthr, rows);  // the roles' shared LDS area (msm.h)
     const size_t waves = (n + 63) / 64 + (na + 63) / 64;
     const unsigned sblk = (unsigned)((n + pthr - 1) / pthr);  // hash workgroups (k_msm_tail's partials)
     const unsigned pblk = rows ? (unsigned)((n + ndec + 3) / 4) : (unsigned)((64 * waves + 255) / 256);
@@ -704,7 +705,7 @@ int msm_launch(Lane& d, EdBuffers& b, size_t n, const uint8_t seed32[32], hipStr
     }
     if (early) {
         NWV_HIP(hipStreamWaitEvent(d.aux, d.pksig_ev, 0));
-        hipLaunchKernelGGL(k_msm_points, dim3(pblk), dim3(pthr), 0, d.aux, gp);
+        hipLaunchKernelGGL(k_msm_points, dim3(pblk), dim3(pthr), plds, d.aux, gp);
         if (spec_tables) {
             const size_t waves2 = 2 * 64 * ((n + 63) / 64);
             hipLaunchKernelGGL(k_ed_points_msm, dim3((unsigned)((waves2 + 255) / 256)), dim3(256), 0, d.aux, (uint64_t)n,
@@ -712,14 +713,14 @@ int msm_launch(Lane& d, EdBuffers& b, size_t n, const uint8_t seed32[32], hipStr
             b.tables_ready = true;
         }
         NWV_HIP(hipEventRecord(d.aux_ev, d.aux));
-        hipLaunchKernelGGL(k_msm_scalars, dim3(sblk), dim3(pthr), 0, stream, gs, p.lay);
+        hipLaunchKernelGGL(k_msm_scalars, dim3(sblk), dim3(pthr), plds, stream, gs, p.lay);
         NWV_HIP(hipStreamWaitEvent(stream, d.aux_ev, 0));
     } else if (fused) {
         if (d.chain_wait) NWV_HIP(hipStreamWaitEvent(stream, d.chain_wait, 0));
-        hipLaunchKernelGGL(k_msm_prep, dim3(sblk + pblk), dim3(pthr), 0, stream, gs, p.lay, gp, sblk);
+        hipLaunchKernelGGL(k_msm_prep, dim3(sblk + pblk), dim3(pthr), plds, stream, gs, p.lay, gp, sblk);
         if (d.chain_rec) NWV_HIP(hipEventRecord(d.chain_rec, stream));
     } else {
-        hipLaunchKernelGGL(k_msm_scalars, dim3(sblk), dim3(pthr), 0, stream, gs, p.lay);
+        hipLaunchKernelGGL(k_msm_scalars, dim3(sblk), dim3(pthr), plds, stream, gs, p.lay);
     }
     if (keyed && !gs.fuse_keysum)
         hipLaunchKernelGGL(k_msm_keysum, dim3((unsigned)b.nkeys_distinct), dim3(256), 0, stream, (uint64_t)n,
@@ -728,7 +729,7 @@ int msm_launch(Lane& d, EdBuffers& b, size_t n, const uint8_t seed32[32], hipStr
                            state);
     if ((rc = mark(1))) return rc;
     if ((rc = mark(2))) return rc;
-    if (!fused && !early) hipLaunchKernelGGL(k_msm_points, dim3(pblk), dim3(pthr), 0, stream, gp);
+    if (!fused && !early) hipLaunchKernelGGL(k_msm_points, dim3(pblk), dim3(pthr), plds, stream, gp);
     if ((rc = mark(3))) return rc;
     const size_t lds_nb = (size_t)4 << (p.lay.cmax - 1);
     uint32_t* kst = b.m_kstart.as<uint32_t>();

@@ -93,6 +93,115 @@ NWV_HD void sc_reduce512(const uint32_t x[16], uint32_t r[8]) {
     for (int i = 0; i < 8; i++) r[i] = rr[i];
 }
 
+// Reduction by folding, for the batch MSM's hash lanes: l = 2^252 + c with c < 2^125 (the four low
+// words of l), so x0 + 2^252 x1 = x0 - c x1 (mod l).  A 512-bit value takes 36 + 20 + 4
+// multiply-adds (two folds and the last step), a 384-bit one 20 + 4, against Barrett's 81 + 45.
+// Both return the canonical residue, word for word what sc_reduce512 returns.
+
+// p[0, N + 4) = c * a[0, N)
+template <int N>
+NWV_HD void sc_mul_c(const uint32_t* a, uint32_t* p) {
+#pragma unroll
+    for (int i = 0; i < N + 4; i++) p[i] = 0;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        uint64_t carry = 0;
+#pragma unroll
+        for (int j = 0; j < N; j++) {
+            uint64_t t = (uint64_t)sc_l(i) * a[j] + p[i + j] + carry;
+            p[i + j] = (uint32_t)t;
+            carry = t >> 32;
+        }
+        p[i + N] = (uint32_t)carry;
+    }
+}
+// h[0, N) = bits [252, 252 + 32 N) of x[0, M)
+template <int N, int M>
+NWV_HD void sc_hi252(const uint32_t* x, uint32_t* h) {
+#pragma unroll
+    for (int k = 0; k < N; k++)
+        h[k] = (7 + k < M ? x[7 + k] >> 28 : 0u) | (8 + k < M ? x[8 + k] << 4 : 0u);
+}
+// word i of 64 l = 2^258 + 64 c (nine words)
+NWV_HD uint32_t sc_l64(int i) {
+    return (i < 8 ? sc_l(i) << 6 : 0u) | (i > 0 ? sc_l(i - 1) >> 26 : 0u);
+}
+// the last step: r = w mod l for 0 <= w < 2^284 (nine words).  With q = w >> 252 (one word) and
+// w0 = w mod 2^252, w0 - c q lies in (-2^157, 2^252): canonical after one conditional + l.
+NWV_HD void sc_fold_last(const uint32_t w[9], uint32_t r[8]) {
+    const uint32_t q = (w[7] >> 28) | (w[8] << 4);
+    uint32_t cq[5];
+    sc_mul_c<1>(&q, cq);
+    uint32_t t[8];
+    int64_t br = 0;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        const int64_t d = (int64_t)(i == 7 ? w[7] & 0x0fffffffu : w[i]) - (i < 5 ? cq[i] : 0u) + br;
+        t[i] = (uint32_t)d;
+        br = d >> 32;
+    }
+    const uint32_t neg = br ? 0xffffffffu : 0u;
+    uint64_t carry = 0;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        carry += (uint64_t)t[i] + (sc_l(i) & neg);
+        r[i] = (uint32_t)carry;
+        carry >>= 32;
+    }
+}
+// r = x mod l for a 512-bit x (16 words).  x1 = x >> 252 < 2^260, t = c x1 < 2^385,
+// t1 = t >> 252 < 2^133, u = c t1 < 2^258:  x = x0 - t0 + u (mod l), and
+// w = x0 - t0 + u + l lies in (0, 2^259).
+NWV_HD void sc_reduce512_fold(const uint32_t x[16], uint32_t r[8]) {
+    uint32_t x1[9], t[13], t1[5], u[9], w[9];
+    sc_hi252<9, 16>(x, x1);
+    sc_mul_c<9>(x1, t);
+    sc_hi252<5, 13>(t, t1);
+    sc_mul_c<5>(t1, u);
+    int64_t c = 0;
+#pragma unroll
+    for (int i = 0; i < 9; i++) {
+        const uint32_t x0 = i < 7 ? x[i] : i == 7 ? x[7] & 0x0fffffffu : 0u;
+        const uint32_t t0 = i < 7 ? t[i] : i == 7 ? t[7] & 0x0fffffffu : 0u;
+        c += (int64_t)x0 + u[i] + (i < 8 ? sc_l(i) : 0u) - t0;
+        w[i] = (uint32_t)c;
+        c >>= 32;
+    }
+    sc_fold_last(w, r);
+}
+// r = x mod l for a 384-bit x (12 words).  x1 = x >> 252 < 2^132, t = c x1 < 2^257:
+// x = x0 - t (mod l), and w = x0 - t + 64 l lies in (2^257, 2^259).
+NWV_HD void sc_reduce384_fold(const uint32_t x[12], uint32_t r[8]) {
+    uint32_t x1[5], t[9], w[9];
+    sc_hi252<5, 12>(x, x1);
+    sc_mul_c<5>(x1, t);
+    int64_t c = 0;
+#pragma unroll
+    for (int i = 0; i < 9; i++) {
+        const uint32_t x0 = i < 7 ? x[i] : i == 7 ? x[7] & 0x0fffffffu : 0u;
+        c += (int64_t)x0 + sc_l64(i) - t[i];
+        w[i] = (uint32_t)c;
+        c >>= 32;
+    }
+    sc_fold_last(w, r);
+}
+// x[0, 12) = z * b for z < 2^128 (four words) and b < 2^256: the batch coefficient times a scalar
+NWV_HD void sc_mul_4x8(const uint32_t z[4], const uint32_t b[8], uint32_t x[12]) {
+#pragma unroll
+    for (int i = 0; i < 12; i++) x[i] = 0;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        uint64_t carry = 0;
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+            uint64_t t = (uint64_t)z[i] * b[j] + x[i + j] + carry;
+            x[i + j] = (uint32_t)t;
+            carry = t >> 32;
+        }
+        x[i + 8] = (uint32_t)carry;
+    }
+}
+
 // r = a * b mod l (a, b < 2^256)
 NWV_HD void sc_mul(const uint32_t a[8], const uint32_t b[8], uint32_t r[8]) {
     uint32_t x[16];
