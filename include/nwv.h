@@ -186,6 +186,12 @@ int nwv_ed25519_verify_batch_keyed_digests(nwv_ctx* ctx, size_t n_pre, const uin
  * through the comb kernel.  Registering the same key list again is a no-op.
  * A full cache leaves further keys uncached; verdicts never depend on the cache. */
 int nwv_keycache_register(nwv_ctx* ctx, size_t n_keys, const uint8_t* keys);
+/* Diagnostics: the key cache of the context's device_index-th device, read under the cache's
+ * lock: out[0] slots in use (slot 0, the basepoint's, included; 0 before the first fill), out[1]
+ * slot capacity (0 before the cache is allocated), out[2] comb tables in use, out[3] comb-table
+ * capacity (env NWV_COMB_KEYS, default 1,024; 0 before the first registration).  Returns the
+ * number of values, 4, or an NWV_ERR_* code (null context, index out of range). */
+int nwv_keycache_stats(const nwv_ctx* ctx, int device_index, uint64_t out[4]);
 
 /* ---- fastcrypto 0.1.2 trait surface (Ed25519 scheme module; contract of
  *      crypto/src/bls12377/mod.rs:264-291 and :485-577) ---- */

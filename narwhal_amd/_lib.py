@@ -75,6 +75,7 @@ def load():
         "nwv_ed25519_verify_batch": ([_vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp], _i32),
         "nwv_ed25519_pubkey_verify": ([_vp, _vp, _vp, _sz, _vp], _i32),
         "nwv_keycache_register": ([_vp, _sz, _vp], _i32),
+        "nwv_keycache_stats": ([_vp, _i32, _vp], _i32),
         "nwv_ed25519_verify_batch_empty_fail": ([_vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp], _i32),
         "nwv_ed25519_aggregate_verify": ([_vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp], _i32),
         "nwv_ed25519_aggregate_batch_verify": ([_vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp], _i32),
@@ -236,6 +237,16 @@ class Engine:
         """nwv_keycache_register: keys, a list of 32-byte keys (the committee, at epoch start)"""
         kb = np.frombuffer(b"".join(keys) or b"\0", dtype=np.uint8)
         _check(self.lib.nwv_keycache_register(self._h, len(keys), _ptr(kb)))
+
+    def keycache_stats(self, device_index=0):
+        """nwv_keycache_stats: {'used': slots in use (slot 0 = B included), 'cap': slot capacity,
+        'comb_used': comb tables in use, 'comb_cap': comb-table capacity} of one device's key cache"""
+        names = ("used", "cap", "comb_used", "comb_cap")
+        out = np.zeros(len(names), dtype=np.uint64)
+        k = self.lib.nwv_keycache_stats(self._h, int(device_index), out.ctypes.data)
+        if k != len(names):
+            _check(k if k < 0 else NWV_ERR_ARG)
+        return {nm: int(v) for nm, v in zip(names, out)}
 
     # ---- Ed25519 ---------------------------------------------------------------------
     def verify_each_arrays(self, pk, sig, arena, offs, lens):

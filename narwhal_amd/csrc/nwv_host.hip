@@ -1483,6 +1483,17 @@ int nwv_diag_counters_ex(const nwv_ctx* ctx, uint64_t* out, int cap) {
     for (int k = 0; k < cap && k < 4; k++) out[k] = v[k];
     return 4;
 }
+int nwv_keycache_stats(const nwv_ctx* ctx, int device_index, uint64_t out[4]) {
+    if (!ctx || !out) return set_err(NWV_ERR_ARG, "null argument");
+    if (device_index < 0 || device_index >= (int)ctx->devs.size()) return set_err(NWV_ERR_ARG, "bad device index");
+    KeyCache& kc = ctx->devs[device_index]->kc;
+    std::lock_guard<std::mutex> g(kc.mu);
+    out[0] = kc.b_ready ? kc.used : 0;  // used is 1 from allocation on; slot 0 is filled with the first misses
+    out[1] = kc.cap;
+    out[2] = kc.comb_used;
+    out[3] = kc.comb_cap;
+    return 4;
+}
 int nwv_set_comb_batch_max(nwv_ctx* ctx, size_t n) {
     if (!ctx) return set_err(NWV_ERR_ARG, "null context");
     ctx->comb_batch_max = std::min<size_t>(n, ctx->shard_min - 1);
