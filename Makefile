@@ -7,6 +7,8 @@ ARCH ?= gfx950
 BLS_SRC := narwhal_amd/csrc/nwv_bls.hip narwhal_amd/csrc/bls381.h narwhal_amd/csrc/bls_verify.h narwhal_amd/csrc/bls_group.h \
 	narwhal_amd/csrc/bls381_consts.h narwhal_amd/csrc/bls381_iso.h narwhal_amd/csrc/bls_wave.h \
 	narwhal_amd/csrc/bls_wave_prog.h narwhal_amd/csrc/bls_shard.h include/nwv_bls.h
+# headers that both engines' translation units include (they stay in CSRC)
+BLS_SHARED := narwhal_amd/csrc/shard.h narwhal_amd/csrc/place.h
 CSRC := $(filter-out $(BLS_SRC),$(wildcard narwhal_amd/csrc/*.h narwhal_amd/csrc/*.hip narwhal_amd/csrc/*.cpp)) \
 	include/nwv.h include/nwv_types.h include/nwv_service.h
 
@@ -22,7 +24,7 @@ narwhal_amd/lib/nwv_service.o: narwhal_amd/csrc/nwv_service.cpp include/nwv.h in
 	@mkdir -p narwhal_amd/lib
 	g++ -O2 -std=c++17 -fPIC -Wall -c -o $@ $<
 # the BLS12-381 engine is its own translation unit (compiled in parallel with the Ed25519 one)
-narwhal_amd/lib/nwv_bls.o: $(BLS_SRC) include/nwv.h
+narwhal_amd/lib/nwv_bls.o: $(BLS_SRC) $(BLS_SHARED) include/nwv.h
 	@mkdir -p narwhal_amd/lib
 	$(HIPCC) --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -c -o $@ narwhal_amd/csrc/nwv_bls.hip
 narwhal_amd/lib/nwv_host.o: $(CSRC)
@@ -38,18 +40,23 @@ oracle:
 	$(MAKE) -C oracle
 
 hostemu: tests/_build/libhostemu.so tests/_build/libsvcstub.so tests/_build/libblsemu.so tests/_build/libblsshard.so \
-	tests/_build/libcombemu.so tests/_build/libfeseeded.so tests/_build/libtrimemu.so tests/_build/libfoldemu.so
+	tests/_build/libcombemu.so tests/_build/libfeseeded.so tests/_build/libtrimemu.so tests/_build/libfoldemu.so \
+	tests/_build/libplace.so
+# the placement policy of a multi-device context (place.h) with no HIP (tests/test_place_host.py)
+tests/_build/libplace.so: tests/hostemu/place_stub.cpp narwhal_amd/csrc/place.h
+	@mkdir -p tests/_build
+	g++ -O1 -g -std=c++17 -fPIC -shared -pthread -o $@ tests/hostemu/place_stub.cpp
 # the BLS and Ed25519 calls' split over a multi-device context (bls_shard.h, shard.h) with stub per-device work
 tests/_build/libblsshard.so: tests/hostemu/bls_shard_stub.cpp narwhal_amd/csrc/bls_shard.h narwhal_amd/csrc/shard.h
 	@mkdir -p tests/_build
 	g++ -O1 -g -std=c++17 -fPIC -shared -pthread -o $@ tests/hostemu/bls_shard_stub.cpp
 # the gfx950 BLS12-381 code compiled for the host (tests/test_bls_hostemu.py)
-tests/_build/libblsemu.so: tests/hostemu/bls_hostemu.cpp $(BLS_SRC)
+tests/_build/libblsemu.so: tests/hostemu/bls_hostemu.cpp $(BLS_SRC) $(BLS_SHARED)
 	@mkdir -p tests/_build
 	$(HIPCC) -std=c++17 -O2 --offload-host-only -x hip -fPIC -shared -o $@ tests/hostemu/bls_hostemu.cpp
 # the same build under AddressSanitizer + UndefinedBehaviorSanitizer (host code only):
 #   make blsemu-asan && tools/run_blsemu_asan.sh
-tests/_build/libblsemu_asan.so: tests/hostemu/bls_hostemu.cpp $(BLS_SRC)
+tests/_build/libblsemu_asan.so: tests/hostemu/bls_hostemu.cpp $(BLS_SRC) $(BLS_SHARED)
 	@mkdir -p tests/_build
 	$(HIPCC) -std=c++17 -O1 -g --offload-host-only -x hip -fPIC -shared -fno-omit-frame-pointer \
 		-fno-gpu-sanitize -fsanitize=address,undefined -fno-sanitize-recover=all -shared-libsan \

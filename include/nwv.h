@@ -124,6 +124,24 @@ int nwv_set_comb_batch_max(nwv_ctx* ctx, size_t n);
 size_t nwv_comb_batch_max(const nwv_ctx* ctx);
 /* HIP ordinal of the context's i-th device (-1 if out of range) */
 int nwv_device_ordinal(const nwv_ctx* ctx, int i);
+/* Placement: which device object of a multi-device context serves a call.  A call that does not
+ * split (fewer than 2 x NWV_SHARD_MIN signatures; every call the protocol makes) goes to the
+ * device with the fewest outstanding ranges, ties to the fewest outstanding items, then to the
+ * lowest index, so a caller that issues one call at a time stays on device 0 and only overlapping
+ * callers spread.  The ranges of a call that splits rotate over the devices from call to call.  A
+ * staged batch counts as one outstanding range on its device from nwv_staged_run until its stream
+ * is next synchronised (nwv_staged_sync, nwv_staged_fetch, nwv_staged_free).  Env NWV_PLACE=first
+ * (read at nwv_init) keeps a single range on device 0 and range k on device k. */
+#define NWV_ENGINE_ED25519 0
+#define NWV_ENGINE_BLS 1
+/* Placement counters of one device object: writes min(cap, count) values, returns count.
+ * [0] ranges placed (a call that does not split is one range)   [1] items in them
+ * [2] ranges outstanding now   [3] peak of [2]   [4] HIP ordinal
+ * [5] device objects of this engine in the context (replica hooks included)
+ * Ed25519 only: [6] tiny  [7] MSM  [8] per-signature  [9] comb batches of this device
+ * [0] and [1] count the engine's own calls; [2] and [3] are the device's load, which both engines
+ * share when they have the same number of device objects. */
+int nwv_diag_device_counters(nwv_ctx* ctx, int engine, int device_index, uint64_t* out, int cap);
 int nwv_abi_version(void);
 /* last error text for this thread (static storage, never NULL) */
 const char* nwv_last_error(void);

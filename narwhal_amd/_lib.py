@@ -67,6 +67,7 @@ def load():
         "nwv_device_count": ([_vp], _i32),
         "nwv_diag_counters": ([_vp, _vp], _i32),
         "nwv_diag_counters_ex": ([_vp, _vp, _i32], _i32),
+        "nwv_diag_device_counters": ([_vp, _i32, _i32, _vp, _i32], _i32),
         "nwv_set_comb_batch_max": ([_vp, _sz], _i32),
         "nwv_comb_batch_max": ([_vp], _sz),
         "nwv_abi_version": ([], _i32),
@@ -224,6 +225,17 @@ class Engine:
         if k < len(names):
             _check(k if k < 0 else NWV_ERR_ARG)
         return {nm: int(v) for nm, v in zip(names, out)}
+
+    def device_counters(self, engine, device_index):
+        """nwv_diag_device_counters: the placement counters of one device object of an engine
+        (0: Ed25519, 1: BLS12-381): {'ranges', 'items', 'outstanding', 'peak', 'ordinal', 'devices'},
+        for Ed25519 also the device's own 'tiny', 'msm', 'each' and 'comb' counts"""
+        names = ("ranges", "items", "outstanding", "peak", "ordinal", "devices", "tiny", "msm", "each", "comb")
+        out = np.zeros(len(names), dtype=np.uint64)
+        k = self.lib.nwv_diag_device_counters(self._h, int(engine), int(device_index), out.ctypes.data, len(names))
+        if k < 6:
+            _check(k if k < 0 else NWV_ERR_ARG)
+        return {nm: int(v) for nm, v in zip(names[:k], out)}
 
     def set_comb_batch_max(self, n):
         """nwv_set_comb_batch_max: the largest registered-key batch that takes the comb path (0: off)"""

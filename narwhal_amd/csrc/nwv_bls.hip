@@ -35,6 +35,7 @@
 #include "../../include/nwv_bls.h"
 #include "bls_verify.h"
 #include "bls_shard.h"
+#include "place.h"
 #include "stage_args.h"
 
 using namespace bls;
@@ -44,6 +45,8 @@ using nwv::bls_shard_ranges;
 __attribute__((visibility("hidden"))) int nwv_internal_set_err(int code, const char* msg);
 extern "C" {  // defined in nwv_host.hip's extern "C" section
 __attribute__((visibility("hidden"))) uint32_t nwv_internal_ctx_flags(const nwv_ctx* ctx);
+__attribute__((visibility("hidden"))) nwv::PlaceTable* nwv_internal_place(nwv_ctx* ctx);
+__attribute__((visibility("hidden"))) int nwv_internal_hip_device(const nwv_ctx* ctx, int i);
 __attribute__((visibility("hidden"))) void nwv_internal_fill_seed(const uint8_t* seed32, uint8_t out[32]);
 }
 
@@ -1067,6 +1070,11 @@ struct BlsDev {
 // one-GPU box too.
 struct BlsCtx {
     std::vector<BlsDev*> devs;
+    // the devices' load (place.h): the Ed25519 engine's table when both engines have the same number
+    // of device objects (device object j of either then counts on entry j, one load per device),
+    // else a table of this engine's own
+    nwv::PlaceTable* place = nullptr;
+    std::unique_ptr<nwv::PlaceTable> own_place;
 };
 std::mutex g_mu;
 std::unordered_map<nwv_ctx*, BlsCtx*> g_devs;
@@ -1079,8 +1087,10 @@ int ctx_of(nwv_ctx* ctx, BlsCtx** out) {
         *out = it->second;
         return NWV_OK;
     }
-    const int nd = nwv_device_count(ctx);
-    if (nd <= 0 || nwv_device_ordinal(ctx, 0) < 0) return nwv_internal_set_err(NWV_ERR_NODEV, "context has no device");
+    // one BlsDev per HIP device of the context times this engine's own replicas (the Ed25519
+    // engine's replicas, NWV_DEVICE_REPLICAS, are that engine's device objects, not devices)
+    const int nd = nwv_internal_hip_device(ctx, -1);
+    if (nd <= 0 || nwv_internal_hip_device(ctx, 0) < 0) return nwv_internal_set_err(NWV_ERR_NODEV, "context has no device");
     static const int replicas = [] {
         const char* e = std::getenv("NWV_BLS_DEVICE_REPLICAS");
         const int r = e ? std::atoi(e) : 1;
@@ -1090,21 +1100,40 @@ int ctx_of(nwv_ctx* ctx, BlsCtx** out) {
     for (int k = 0; k < nd; k++)
         for (int r = 0; r < replicas; r++) {
             auto* d = new BlsDev;
-            d->ordinal = nwv_device_ordinal(ctx, k);
+            d->ordinal = nwv_internal_hip_device(ctx, k);
             d->flags = nwv_internal_ctx_flags(ctx);
             c->devs.push_back(d);
         }
+    nwv::PlaceTable* shared = nwv_internal_place(ctx);
+    if (shared && shared->size() == c->devs.size()) {
+        c->place = shared;
+    } else {
+        c->own_place.reset(new nwv::PlaceTable(c->devs.size(), nwv::place_mode_from_env()));
+        c->place = c->own_place.get();
+    }
     g_devs[ctx] = c;
     *out = c;
     return NWV_OK;
 }
 
-// the context's first device (single-device entry points: aggregate, keygen, sign, hash, pairing)
+// the context's first device (single-device entry points: keygen, sign, hash, pairing)
 int dev_of(nwv_ctx* ctx, BlsDev** out) {
     BlsCtx* c;
     int rc = ctx_of(ctx, &c);
     if (rc) return rc;
     *out = c->devs[0];
+    return NWV_OK;
+}
+
+// the device that served the calling thread's last nwv_bls_verify_many on a context (range 0's, when
+// the call split): what nwv_bls_last_kernel_ms / _last_path / _last_keys read; device 0 if none
+thread_local std::unordered_map<const nwv_ctx*, size_t> t_last_dev;
+int last_dev_of(nwv_ctx* ctx, BlsDev** out) {
+    BlsCtx* c;
+    int rc = ctx_of(ctx, &c);
+    if (rc) return rc;
+    const auto it = t_last_dev.find(ctx);
+    *out = c->devs[(it != t_last_dev.end() && it->second < c->devs.size()) ? it->second : 0];
     return NWV_OK;
 }
 
@@ -1648,6 +1677,21 @@ __attribute__((visibility("hidden"))) void nwv_bls_ctx_release(nwv_ctx* ctx) {
     g_devs.erase(it);
 }
 
+// nwv_diag_device_counters of the BLS12-381 engine (values [0, 6), include/nwv.h)
+__attribute__((visibility("hidden"))) int nwv_bls_device_counters(nwv_ctx* ctx, int device_index, uint64_t* out,
+                                                                  int cap) {
+    BlsCtx* c;
+    int rc = ctx_of(ctx, &c);
+    if (rc) return rc;
+    if (device_index < 0 || device_index >= (int)c->devs.size())
+        return nwv_internal_set_err(NWV_ERR_ARG, "bad device index");
+    const nwv::PlaceEntry e = c->place->get((size_t)device_index);
+    const uint64_t v[6] = {e.ranges[NWV_ENGINE_BLS], e.items[NWV_ENGINE_BLS], e.out_ranges, e.peak,
+                           (uint64_t)c->devs[device_index]->ordinal, c->devs.size()};
+    for (int k = 0; k < cap && k < 6; k++) out[k] = v[k];
+    return 6;
+}
+
 extern "C" {
 
 int nwv_bls_verify_many(nwv_ctx* ctx, size_t n_keys, const uint8_t* keys, size_t n, const uint8_t* sigs,
@@ -1673,15 +1717,18 @@ int nwv_bls_verify_many(nwv_ctx* ctx, size_t n_keys, const uint8_t* keys, size_t
     BlsCtx* c;
     int rc = ctx_of(ctx, &c);
     if (rc) return rc;
-    // items split by index over the context's devices (bls_shard.h); small calls stay on device 0
+    // items split by index over the context's devices (bls_shard.h); a small call is one range on
+    // the least-loaded device, the ranges of a larger one rotate (place.h)
     static const size_t shard_min = [] {
         const char* e = std::getenv("NWV_BLS_SHARD_MIN");
         return e ? (size_t)std::strtoull(e, nullptr, 10) : (size_t)256;
     }();
     const auto ranges = bls_shard_ranges(n, c->devs.size(), shard_min);
+    const auto tickets = nwv::place_ranges(*c->place, ranges, NWV_ENGINE_BLS);
+    t_last_dev[ctx] = tickets[0].dev();
     if (ranges.size() == 1)
-        return verify_on(*c->devs[0], n_keys, keys, n, sigs, pk_off, pk_cnt, pk_idx, n_idx, msg_base, msg_off, msg_len,
-                         msg_bytes, dst, dst_len, status);
+        return verify_on(*c->devs[tickets[0].dev()], n_keys, keys, n, sigs, pk_off, pk_cnt, pk_idx, n_idx, msg_base,
+                         msg_off, msg_len, msg_bytes, dst, dst_len, status);
     std::vector<std::string> err(ranges.size());
     rc = bls_for_ranges(ranges, [&](size_t k, size_t lo, size_t hi) -> int {
         size_t ni = 0, mb = 0;  // the range's own key-index and message extents
@@ -1689,8 +1736,9 @@ int nwv_bls_verify_many(nwv_ctx* ctx, size_t n_keys, const uint8_t* keys, size_t
             ni = std::max<size_t>(ni, (size_t)pk_off[i] + pk_cnt[i]);
             mb = std::max<size_t>(mb, msg_off[i] + msg_len[i]);
         }
-        const int e = verify_on(*c->devs[k], n_keys, keys, hi - lo, sigs + 48 * lo, pk_off + lo, pk_cnt + lo, pk_idx,
-                                ni, msg_base, msg_off + lo, msg_len + lo, mb, dst, dst_len, status + lo);
+        const int e = verify_on(*c->devs[tickets[k].dev()], n_keys, keys, hi - lo, sigs + 48 * lo, pk_off + lo,
+                                pk_cnt + lo, pk_idx, ni, msg_base, msg_off + lo, msg_len + lo, mb, dst, dst_len,
+                                status + lo);
         if (e) err[k] = nwv_last_error();
         return e;
     });
@@ -1703,7 +1751,7 @@ int nwv_bls_verify_many(nwv_ctx* ctx, size_t n_keys, const uint8_t* keys, size_t
 int nwv_bls_last_kernel_ms(nwv_ctx* ctx, double out_ms[5]) {
     if (!out_ms) return nwv_internal_set_err(NWV_ERR_ARG, "null argument");
     BlsDev* d;
-    int rc = dev_of(ctx, &d);
+    int rc = last_dev_of(ctx, &d);
     if (rc) return rc;
     std::lock_guard<std::mutex> g(d->stat_mu);
     for (int k = 0; k < 5; k++) out_ms[k] = d->last_ms[k];
@@ -1712,7 +1760,7 @@ int nwv_bls_last_kernel_ms(nwv_ctx* ctx, double out_ms[5]) {
 
 int nwv_bls_last_path(nwv_ctx* ctx) {
     BlsDev* d;
-    int rc = dev_of(ctx, &d);
+    int rc = last_dev_of(ctx, &d);
     if (rc) return rc;
     std::lock_guard<std::mutex> g(d->stat_mu);
     return d->last_path;
@@ -1721,7 +1769,7 @@ int nwv_bls_last_path(nwv_ctx* ctx) {
 int nwv_bls_last_keys(nwv_ctx* ctx, uint64_t out[2]) {
     if (!out) return nwv_internal_set_err(NWV_ERR_ARG, "null argument");
     BlsDev* d;
-    int rc = dev_of(ctx, &d);
+    int rc = last_dev_of(ctx, &d);
     if (rc) return rc;
     std::lock_guard<std::mutex> g(d->stat_mu);
     out[0] = d->last_keys[0];
@@ -1785,9 +1833,29 @@ int nwv_bls_aggregate(nwv_ctx* ctx, size_t n, const uint8_t* sigs48, uint8_t out
     if (n == 0) return NWV_ERR_SIGNATURE;
     if (!sigs48 || !out48) return nwv_internal_set_err(NWV_ERR_ARG, "null argument");
     if (n > (1u << 26)) return nwv_internal_set_err(NWV_ERR_ARG, "batch too large");
-    BlsDev* d;
-    int rc = dev_of(ctx, &d);
+    BlsCtx* c;
+    int rc = ctx_of(ctx, &c);
     if (rc) return rc;
+    // the first device, in index order, whose verified-signature ring holds every signature of the
+    // call (a host-side lookup; the ring is read again below, under the lock the kernels run
+    // under); none: the least-loaded device, which decodes them
+    size_t holder = c->devs.size();
+    if (c->devs.size() > 1 && n <= SC_CAP && !(c->devs[0]->flags & NWV_FLAG_NO_SIGCACHE))
+        for (size_t j = 0; j < c->devs.size() && holder == c->devs.size(); j++) {
+            BlsSigCache& sc = c->devs[j]->sc;
+            std::shared_lock<std::shared_mutex> hold(sc.mu);
+            if (!sc.rec.p) continue;
+            bool all = true;
+            Sig48 k;
+            for (size_t i = 0; i < n && all; i++) {
+                std::memcpy(k.b, sigs48 + 48 * i, 48);
+                all = sc.slot.find(k) != sc.slot.end();
+            }
+            if (all) holder = j;
+        }
+    const nwv::Ticket ticket = holder < c->devs.size() ? nwv::Ticket(*c->place, holder, (uint64_t)n, NWV_ENGINE_BLS)
+                                                       : nwv::Ticket(*c->place, (uint64_t)n, NWV_ENGINE_BLS);
+    BlsDev* d = c->devs[ticket.dev()];
     LaneLease lane(*d);
     if ((rc = lane.rc())) return rc;
     BlsLane& L = *lane;

@@ -11,6 +11,7 @@
 #include <chrono>
 #include <condition_variable>
 #include <functional>
+#include <memory>
 #include <cstdio>
 #include <cstring>
 #include <mutex>
@@ -25,6 +26,7 @@
 #include "msm_kernels.hip"
 #include "tiny_kernels.hip"
 #include "comb_kernels.hip"
+#include "place.h"
 #include "shard.h"
 #include "stage_args.h"
 
@@ -49,6 +51,8 @@ void htrace(const char* what) {
 }  // namespace
 // shared with the BLS12-381 translation unit (nwv_bls.hip); not part of the public ABI
 __attribute__((visibility("hidden"))) void nwv_bls_ctx_release(nwv_ctx* ctx);
+__attribute__((visibility("hidden"))) int nwv_bls_device_counters(nwv_ctx* ctx, int device_index, uint64_t* out,
+                                                                  int cap);
 __attribute__((visibility("hidden"))) int nwv_internal_set_err(int code, const char* msg) {
     g_last_error = msg;
     return code;
@@ -1325,6 +1329,7 @@ bool verdicts_all_valid(const uint64_t* bits, size_t n) {
 
 struct nwv_ctx {
     std::vector<Gpu*> devs;
+    std::vector<int> ordinals;  // the HIP devices the context was opened over (devs counts replicas too)
     // a call splits over the devices only into ranges of at least this many signatures
     // (shard.h; env NWV_SHARD_MIN, read at nwv_init)
     size_t shard_min = 16384;
@@ -1332,6 +1337,9 @@ struct nwv_ctx {
     // registered-key batches of TINY_MAX < n <= comb_batch_max signatures take k_ed_comb
     // (nwv_set_comb_batch_max; 0: off; always below shard_min, so only single-range calls)
     std::atomic<size_t> comb_batch_max{NWV_COMB_BATCH_MAX_DEFAULT};
+    // the load of every device object, by which calls are placed (place.h; env NWV_PLACE, read at
+    // nwv_init); the BLS12-381 engine shares it when it has as many device objects
+    std::shared_ptr<nwv::PlaceTable> place;
 };
 
 // Per-kernel device time of the staged pipelines (HIP events on the batch's own stream).
@@ -1375,13 +1383,31 @@ struct nwv_staged {
     hipEvent_t seed_ev[SEED_SLOTS] = {};
     uint64_t seed_runs = 0;
     std::vector<hipEvent_t> marks;  // nwv_staged_mark: step-completion timestamps on this stream
+    // from nwv_staged_run until the stream is next synchronised the batch is one outstanding range
+    // on its device (one flag per batch: a loop of runs between two syncs tests it once per run)
+    size_t dev_index = 0;
+    std::shared_ptr<nwv::PlaceTable> place;  // (a batch may outlive its context)
+    nwv::Ticket load;
 };
 
 // Shard [0, n) into contiguous, 64-aligned ranges of at least ctx->shard_min signatures over the
 // context's devices (shard.h) and run fn(lane, lo, hi) for each: range 0 on the calling thread, the
-// others on one host thread each.  A call below 2 shard_min runs on device 0 alone.
+// others on one host thread each.  A call below 2 shard_min is one range, on the least-loaded
+// device; the ranges of a larger call rotate over the devices (place.h).  Every range holds its
+// ticket, taken before its lane is leased, until the call returns.
 template <class Fn>
 static int for_shards(nwv_ctx* ctx, size_t n, Fn fn) {
+    const auto ranges = nwv::ed_shard_ranges(n, ctx->devs.size(), ctx->shard_min);
+    const auto tickets = nwv::place_ranges(*ctx->place, ranges);
+    return nwv::for_ranges(ranges, [&](size_t k, size_t lo, size_t hi) -> int {
+        LaneRef lane(*ctx->devs[tickets[k].dev()]);
+        const int rc = lane.rc();
+        return rc ? rc : fn(*lane, lo, hi);
+    });
+}
+// The same with range k on device k and no ticket (nwv_ed25519_sign_many: tooling).
+template <class Fn>
+static int for_shards_fixed(nwv_ctx* ctx, size_t n, Fn fn) {
     const auto ranges = nwv::ed_shard_ranges(n, ctx->devs.size(), ctx->shard_min);
     return nwv::for_ranges(ranges, [&](size_t k, size_t lo, size_t hi) -> int {
         LaneRef lane(*ctx->devs[k]);
@@ -1404,8 +1430,9 @@ static size_t env_size(const char* name, size_t dflt, size_t lo, size_t hi) {
 
 // Test hook: env NWV_DEVICE_REPLICAS=r (read at nwv_init, 1..8) opens r independent device
 // objects (own lanes, key cache, basepoint tables) per ordinal, so the multi-device split of
-// for_shards -- ranges, per-range seeds, verdict words at lo / 64, the rc merge -- runs on a
-// one-GPU box exactly as it does over r real devices.
+// for_shards -- ranges, placement, per-range seeds, verdict words at lo / 64, the rc merge -- runs
+// on a one-GPU box exactly as it does over r real devices.  nwv_diag_device_counters reports the
+// number of device objects, so a stray replica variable is visible.
 static int init_devices(nwv_ctx** out, std::vector<int> ordinals, uint32_t flags) {
     if (!out) return set_err(NWV_ERR_ARG, "null out");
     *out = nullptr;
@@ -1415,6 +1442,7 @@ static int init_devices(nwv_ctx** out, std::vector<int> ordinals, uint32_t flags
     ctx->b2_shard_min = env_size("NWV_B2_SHARD_MIN", ctx->b2_shard_min, 1, SIZE_MAX);
     ctx->comb_batch_max = std::min<size_t>(NWV_COMB_BATCH_MAX_DEFAULT, ctx->shard_min - 1);
     const size_t replicas = env_size("NWV_DEVICE_REPLICAS", 1, 1, 8);
+    ctx->ordinals = ordinals;
     for (int o : ordinals)
         for (size_t r = 0; r < replicas; r++) {
             auto* d = new Gpu;
@@ -1427,6 +1455,7 @@ static int init_devices(nwv_ctx** out, std::vector<int> ordinals, uint32_t flags
             }
             ctx->devs.push_back(d);
         }
+    ctx->place.reset(new nwv::PlaceTable(ctx->devs.size(), nwv::place_mode_from_env()));
     *out = ctx;
     return NWV_OK;
 }
@@ -1503,6 +1532,26 @@ size_t nwv_comb_batch_max(const nwv_ctx* ctx) { return ctx ? ctx->comb_batch_max
 int nwv_device_ordinal(const nwv_ctx* ctx, int i) {
     return (ctx && i >= 0 && i < (int)ctx->devs.size()) ? ctx->devs[i]->ordinal : -1;
 }
+int nwv_diag_device_counters(nwv_ctx* ctx, int engine, int device_index, uint64_t* out, int cap) {
+    if (!ctx || (cap > 0 && !out) || cap < 0) return set_err(NWV_ERR_ARG, "bad argument");
+    if (engine == NWV_ENGINE_BLS) return nwv_bls_device_counters(ctx, device_index, out, cap);
+    if (engine != NWV_ENGINE_ED25519) return set_err(NWV_ERR_ARG, "bad engine");
+    if (device_index < 0 || device_index >= (int)ctx->devs.size()) return set_err(NWV_ERR_ARG, "bad device index");
+    const Gpu* g = ctx->devs[device_index];
+    const nwv::PlaceEntry e = ctx->place->get((size_t)device_index);
+    const uint64_t v[10] = {e.ranges[NWV_ENGINE_ED25519],
+                            e.items[NWV_ENGINE_ED25519],
+                            e.out_ranges,
+                            e.peak,
+                            (uint64_t)g->ordinal,
+                            ctx->devs.size(),
+                            g->n_tiny.load(),
+                            g->n_msm.load(),
+                            g->n_each.load(),
+                            g->n_comb.load()};
+    for (int k = 0; k < cap && k < 10; k++) out[k] = v[k];
+    return 10;
+}
 
 int nwv_ed25519_verify_each(nwv_ctx* ctx, size_t n, const uint8_t* pk, const uint8_t* sig,
                             const uint8_t* msg_base, const uint64_t* msg_off,
@@ -1572,6 +1621,16 @@ static void fill_seed(const uint8_t* seed32, uint8_t out[32]) {
 // shared with nwv_bls.hip (hidden): the context's nwv_init flags, and a batch-coefficient seed
 __attribute__((visibility("hidden"))) uint32_t nwv_internal_ctx_flags(const nwv_ctx* ctx) {
     return (ctx && !ctx->devs.empty()) ? ctx->devs[0]->flags : 0u;
+}
+// the context's load table (one entry per Ed25519 device object), and the HIP devices the context
+// was opened over (i < 0: how many; the replicas of NWV_DEVICE_REPLICAS are not counted)
+__attribute__((visibility("hidden"))) nwv::PlaceTable* nwv_internal_place(nwv_ctx* ctx) {
+    return ctx ? ctx->place.get() : nullptr;
+}
+__attribute__((visibility("hidden"))) int nwv_internal_hip_device(const nwv_ctx* ctx, int i) {
+    if (!ctx) return -1;
+    if (i < 0) return (int)ctx->ordinals.size();
+    return i < (int)ctx->ordinals.size() ? ctx->ordinals[i] : -1;
 }
 __attribute__((visibility("hidden"))) void nwv_internal_fill_seed(const uint8_t* seed32, uint8_t out[32]) {
     fill_seed(seed32, out);
@@ -2111,6 +2170,8 @@ static int staged_create(nwv_ctx* ctx, int device_index, size_t n, nwv_staged** 
     if (!st) return set_err(NWV_ERR_OOM, "staged allocation");
     st->ctx = ctx;
     st->gpu = ctx->devs[device_index];
+    st->dev_index = (size_t)device_index;
+    st->place = ctx->place;
     st->n = n;
     int rc;
     {
@@ -2245,6 +2306,7 @@ int nwv_staged_run(nwv_staged* st, int mode, const uint8_t seed32[32]) {
     std::lock_guard<std::mutex> g(st->mu);
     int rc = with_device(st->own);
     if (rc) return rc;
+    if (!st->load.held()) st->load = nwv::Ticket(*st->place, st->dev_index, (uint64_t)st->n, NWV_ENGINE_ED25519);
     if ((rc = staged_collect_times(st))) return rc;
     if (mode == 1) {
         uint8_t seed[32];
@@ -2301,7 +2363,9 @@ int nwv_staged_run(nwv_staged* st, int mode, const uint8_t seed32[32]) {
 static int staged_sync_locked(nwv_staged* st) {
     int rc = with_device(st->own);
     if (rc) return rc;
-    NWV_HIP(hipStreamSynchronize(st->stream));
+    const hipError_t e = hipStreamSynchronize(st->stream);
+    st->load.release();  // nothing of the batch is in flight any more
+    NWV_HIP(e);
     return staged_collect_times(st);
 }
 
@@ -2441,6 +2505,7 @@ void nwv_staged_free(nwv_staged* st) {
         std::lock_guard<std::mutex> g(st->mu);
         (void)hipSetDevice(st->own.ordinal);
         if (st->stream) (void)hipStreamSynchronize(st->stream);
+        st->load.release();
         if (st->graph) (void)hipGraphExecDestroy(st->graph);
         for (auto& e : st->seed_ev)
             if (e) (void)hipEventDestroy(e);
@@ -2544,8 +2609,9 @@ int nwv_blake2b256_many(nwv_ctx* ctx, size_t n, const uint8_t* base, const uint6
     static const uint8_t empty[1] = {0};
     if (!base) base = empty;
     const auto ranges = nwv::shard_ranges(n, ctx->devs.size(), ctx->b2_shard_min, 1);
+    const auto tickets = nwv::place_ranges(*ctx->place, ranges);
     return nwv::for_ranges(ranges, [&](size_t k, size_t lo, size_t hi) -> int {
-        LaneRef lane(*ctx->devs[k]);
+        LaneRef lane(*ctx->devs[tickets[k].dev()]);
         Lane& d = *lane;
         std::vector<uint64_t> roff;
         int rc = lane.rc();
@@ -2585,7 +2651,7 @@ int nwv_ed25519_verify_batch_keyed_digests(nwv_ctx* ctx, size_t n_pre, const uin
     for (size_t i = 0; i < n; i++) moff[i] = 32ull * digest_idx[i];
     if (nwv::ed_shard_ranges(n, ctx->devs.size(), ctx->shard_min).size() > 1 || n_pre == 0 || n == 0) {
         // a batch that splits over several devices: the digests come back to the host and the
-        // signatures are sharded (a smaller one stays fused on device 0, below)
+        // signatures are sharded (a smaller one stays fused on one device, placed by load, below)
         int rc = nwv_blake2b256_many(ctx, n_pre, pre_base, pre_off, pre_len, digests_out);
         if (rc || n == 0) return rc;
         return nwv_ed25519_verify_batch_keyed(ctx, n_keys, keys, n, key_idx, sig, digests_out, moff.data(),
@@ -2595,7 +2661,8 @@ int nwv_ed25519_verify_batch_keyed_digests(nwv_ctx* ctx, size_t n_pre, const uin
     if (!pre_base) pre_base = empty;
     uint8_t seed[32];
     fill_seed(seed32, seed);
-    LaneRef lane(*ctx->devs[0]);
+    const nwv::Ticket ticket(*ctx->place, (uint64_t)n);
+    LaneRef lane(*ctx->devs[ticket.dev()]);
     Lane& d = *lane;
     int rc = lane.rc();
     std::vector<uint64_t> roff;
@@ -2630,7 +2697,8 @@ int nwv_batch_digest_serialized(nwv_ctx* ctx, size_t n, const uint8_t* base, con
     if (!ctx || (n && (!base || !off || !len || !out || !err_offset)))
         return set_err(NWV_ERR_ARG, "null argument");
     if (n == 0) return NWV_OK;
-    LaneRef lane(*ctx->devs[0]);
+    const nwv::Ticket ticket(*ctx->place, (uint64_t)n);
+    LaneRef lane(*ctx->devs[ticket.dev()]);
     Lane& d = *lane;
     int rc = lane.rc();
     std::vector<uint64_t> roff;
@@ -2667,7 +2735,7 @@ int nwv_ed25519_sign_many(nwv_ctx* ctx, size_t n, const uint8_t* seeds, const ui
     if (n == 0) return NWV_OK;
     static const uint8_t empty[1] = {0};
     if (!msg_base) msg_base = empty;
-    return for_shards(ctx, n, [&](Lane& d, size_t lo, size_t hi) -> int {
+    return for_shards_fixed(ctx, n, [&](Lane& d, size_t lo, size_t hi) -> int {
         // messages via the Ed25519 staging; seeds go to kbuf, outputs come back in pk / sig
         int rc = ed_stage(d, d.ed, lo, hi, nullptr, nullptr, msg_base, msg_off, msg_len, nullptr);
         if (rc) return rc;

@@ -11,7 +11,7 @@
 //   * a range holds at least min_per items.  A batch MSM's tail is a latency-bound chain of
 //     ~0.12 ms whatever the batch size, so eight 128-signature MSMs on eight devices (plus their
 //     host threads) are slower than one 1,024-signature MSM on one: a call of fewer than
-//     2 min_per items stays on device 0.
+//     2 min_per items is one range, which goes to the least-loaded device (place.h).
 #pragma once
 #include <cstddef>
 #include <thread>
@@ -22,7 +22,8 @@ namespace nwv {
 
 // [lo, hi) ranges over at most ndev devices: contiguous, in order, near-equal (counted in units of
 // `align` items), every start a multiple of align, each range at least min_per items (except that a
-// call of n < 2 min_per items is one range).  Range k runs on device k.
+// call of n < 2 min_per items is one range).  place.h maps the ranges to devices: a single range by
+// load, several ranges rotated over the devices.
 inline std::vector<std::pair<size_t, size_t>> shard_ranges(size_t n, size_t ndev, size_t min_per, size_t align) {
     std::vector<std::pair<size_t, size_t>> r;
     if (n == 0) return r;

@@ -32,6 +32,9 @@ pub const NWV_ERR_EMPTY: c_int = -5;
 pub const NWV_ERR_LENGTH: c_int = -6;
 pub const NWV_ERR_REENTRANT: c_int = -7;
 pub const NWV_ABI_VERSION: c_int = 1;
+// nwv_diag_device_counters: the engine whose device objects are meant
+pub const NWV_ENGINE_ED25519: c_int = 0;
+pub const NWV_ENGINE_BLS: c_int = 1;
 // nwv_init flags
 pub const NWV_FLAG_MSM_ALWAYS: u32 = 1;
 pub const NWV_FLAG_MSM_NEVER: u32 = 2;
@@ -182,6 +185,13 @@ extern "C" {
     pub fn nwv_set_comb_batch_max(ctx: *mut NwvCtx, n: usize) -> c_int;
     pub fn nwv_comb_batch_max(ctx: *const NwvCtx) -> usize;
     pub fn nwv_device_ordinal(ctx: *const NwvCtx, i: c_int) -> c_int;
+    pub fn nwv_diag_device_counters(
+        ctx: *mut NwvCtx,
+        engine: c_int,
+        device_index: c_int,
+        out: *mut u64,
+        cap: c_int,
+    ) -> c_int;
     pub fn nwv_abi_version() -> c_int;
     pub fn nwv_last_error() -> *const c_char;
     // ---- Ed25519 verification (include/nwv.h)
