@@ -41,7 +41,12 @@ oracle:
 
 hostemu: tests/_build/libhostemu.so tests/_build/libsvcstub.so tests/_build/libblsemu.so tests/_build/libblsshard.so \
 	tests/_build/libcombemu.so tests/_build/libfeseeded.so tests/_build/libtrimemu.so tests/_build/libfoldemu.so \
-	tests/_build/libplace.so
+	tests/_build/libplace.so tests/_build/libkcalloc.so
+# the key cache's slot / table bookkeeping and its hold (keycache_alloc.h) with no HIP
+# (tests/test_keycache_alloc_host.py)
+tests/_build/libkcalloc.so: tests/hostemu/keycache_alloc_stub.cpp narwhal_amd/csrc/keycache_alloc.h
+	@mkdir -p tests/_build
+	g++ -O1 -g -std=c++17 -fPIC -shared -pthread -o $@ tests/hostemu/keycache_alloc_stub.cpp
 # the placement policy of a multi-device context (place.h) with no HIP (tests/test_place_host.py)
 tests/_build/libplace.so: tests/hostemu/place_stub.cpp narwhal_amd/csrc/place.h
 	@mkdir -p tests/_build

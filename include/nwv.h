@@ -202,11 +202,29 @@ int nwv_ed25519_verify_batch_keyed_digests(nwv_ctx* ctx, size_t n_pre, const uin
  * Vote::verify -- through the one-launch path, and larger ones of at most nwv_comb_batch_max
  * signatures -- a large committee's certificate, a round's votes, validate_certificates --
  * through the comb kernel.  Registering the same key list again is a no-op.
- * A full cache leaves further keys uncached; verdicts never depend on the cache. */
+ * A full cache leaves further keys uncached; verdicts never depend on the cache.  Slots and
+ * tables are handed out until nwv_keycache_retain gives some back: call it at every epoch change,
+ * before registering the new committee. */
 int nwv_keycache_register(nwv_ctx* ctx, size_t n_keys, const uint8_t* keys);
+/* Epoch change: on every device of the context, retire every cached key that is NOT in keys
+ * (n_keys x 32; n_keys = 0, keys NULL: retire all).  A retired key's slot and comb table are
+ * free for later keys.  Registers nothing: call nwv_keycache_register for the new committee
+ * afterwards.  out_or_null[4], summed over the devices: [0] slots retired, [1] comb tables
+ * retired, [2] slots kept only because a live staged batch reads them, [3] slots in use after
+ * (slot 0 included).  Verdicts never depend on it.
+ * Keys of the list that are not cached are ignored, duplicates are allowed, and slot 0 (the
+ * basepoint) is never retired.  Validators that stay keep their records and tables.  The call
+ * waits for the keyed calls in flight on each device (they hold the cache until their kernels
+ * have finished) and new ones wait for it, so it completes under continuous callers.  A staged
+ * keyed batch (nwv_stage_ed25519_keyed) pins the slots it reads until nwv_staged_free: its keys
+ * are kept, with their tables, and go at the first retain after it is freed.  If a retired key
+ * belonged to the last fully registered list, registering that list again does the work again.
+ * A context opened with NWV_FLAG_NO_KEYCACHE: a successful no-op, out all zero. */
+int nwv_keycache_retain(nwv_ctx* ctx, size_t n_keys, const uint8_t* keys, uint64_t* out_or_null);
 /* Diagnostics: the key cache of the context's device_index-th device, read under the cache's
- * lock: out[0] slots in use (slot 0, the basepoint's, included; 0 before the first fill), out[1]
- * slot capacity (0 before the cache is allocated), out[2] comb tables in use, out[3] comb-table
+ * lock: out[0] slots in use now (slot 0, the basepoint's, included; 0 before the first fill;
+ * retired slots do not count), out[1] slot capacity (0 before the cache is allocated), out[2]
+ * comb tables in use now, out[3] comb-table
  * capacity (env NWV_COMB_KEYS, default 1,024; 0 before the first registration).  Returns the
  * number of values, 4, or an NWV_ERR_* code (null context, index out of range). */
 int nwv_keycache_stats(const nwv_ctx* ctx, int device_index, uint64_t out[4]);

@@ -77,6 +77,7 @@ def load():
         "nwv_ed25519_pubkey_verify": ([_vp, _vp, _vp, _sz, _vp], _i32),
         "nwv_keycache_register": ([_vp, _sz, _vp], _i32),
         "nwv_keycache_stats": ([_vp, _i32, _vp], _i32),
+        "nwv_keycache_retain": ([_vp, _sz, _vp, _vp], _i32),
         "nwv_ed25519_verify_batch_empty_fail": ([_vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp], _i32),
         "nwv_ed25519_aggregate_verify": ([_vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp], _i32),
         "nwv_ed25519_aggregate_batch_verify": ([_vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp], _i32),
@@ -249,6 +250,17 @@ class Engine:
         """nwv_keycache_register: keys, a list of 32-byte keys (the committee, at epoch start)"""
         kb = np.frombuffer(b"".join(keys) or b"\0", dtype=np.uint8)
         _check(self.lib.nwv_keycache_register(self._h, len(keys), _ptr(kb)))
+
+    def keycache_retain(self, keys):
+        """nwv_keycache_retain (epoch change): retire every cached key that is not in keys, a list of
+        32-byte keys (empty: retire all); register the new committee afterwards.  Returns, summed
+        over the devices, {'slots_retired', 'combs_retired', 'pinned_kept': slots kept only because a
+        live staged batch reads them, 'used': slots in use after (slot 0 = B included)}"""
+        kb = np.frombuffer(b"".join(keys), dtype=np.uint8) if keys else None
+        names = ("slots_retired", "combs_retired", "pinned_kept", "used")
+        out = np.zeros(len(names), dtype=np.uint64)
+        _check(self.lib.nwv_keycache_retain(self._h, len(keys), _ptr(kb) if keys else None, out.ctypes.data))
+        return {nm: int(v) for nm, v in zip(names, out)}
 
     def keycache_stats(self, device_index=0):
         """nwv_keycache_stats: {'used': slots in use (slot 0 = B included), 'cap': slot capacity,

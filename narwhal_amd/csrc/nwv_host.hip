@@ -26,6 +26,7 @@
 #include "msm_kernels.hip"
 #include "tiny_kernels.hip"
 #include "comb_kernels.hip"
+#include "keycache_alloc.h"
 #include "place.h"
 #include "shard.h"
 #include "stage_args.h"
@@ -203,6 +204,12 @@ struct Lane {
     hipEvent_t chain_wait = nullptr, chain_rec = nullptr;
     DevBuf tiny_ws;  // k_ed_tiny's workspace (zeroed once; the kernel leaves it zeroed)
     DevBuf comb_ws;  // k_ed_comb's (zeroed when it is allocated or grows; the kernel leaves it zeroed)
+    // the call's hold on its device's key cache (kc_hold_shared / kc_hold_excl), released when the
+    // lane goes back to the pool; kc_unsynced: the call has not yet reached a point where its
+    // stream is known to be drained (cleared by kc_call_done), so the release waits for it
+    enum { KC_NONE = 0, KC_SHARED = 1, KC_EXCL = 2 };
+    int kc_held = KC_NONE;
+    bool kc_unsynced = false;
 };
 
 // Committee key cache of a device.  fastcrypto decompresses a public key once, when it is
@@ -210,44 +217,25 @@ struct Lane {
 // so each key's point record and that of 2^128 A are computed once (k_keycache_fill) and kept
 // in HBM.  A keyed batch whose keys are all cached then carries every MSM scalar in 128 bits
 // (K = lo + 2^128 hi on A and 2^128 A, the same for B): half the windows and half the final
-// doubling chain, and no key decompression in k_msm_prep.  Slots are append-only (a slot in
-// use by an in-flight or captured batch is never rewritten); when the cache is full a call
-// uses the uncached form.  Slot 0 holds B.
-struct Key32 {
-    uint8_t b[32];
-    bool operator==(const Key32& o) const { return std::memcmp(b, o.b, 32) == 0; }
-};
-// All 32 key bytes, mixed with a per-process random seed: keys chosen to collide in the map
-// would otherwise make every lookup under the cache lock linear.
-struct Key32Hash {
-    size_t operator()(const Key32& k) const {
-        static const uint64_t seed = [] {
-            std::random_device rd;
-            return ((uint64_t)rd() << 32) ^ rd() ^ 0x9E3779B97F4A7C15ull;
-        }();
-        uint64_t h = seed;
-        for (int i = 0; i < 4; i++) {
-            uint64_t w;
-            std::memcpy(&w, k.b + 8 * i, 8);
-            h = (h ^ w) * 0xFF51AFD7ED558CCDull;
-            h ^= h >> 32;
-        }
-        return (size_t)h;
-    }
-};
+// doubling chain, and no key decompression in k_msm_prep.  Slots are appended until
+// nwv_keycache_retain gives some back (a slot in use by an in-flight or captured batch is never
+// rewritten: in-flight calls hold the cache, staged batches pin their slots); when the cache is
+// full a call uses the uncached form.  Slot 0 holds B.
+using nwv::Key32;  // (keycache_alloc.h, with its seeded hash)
 struct KeyCache {
     std::mutex mu;
-    std::unordered_map<Key32, uint32_t, Key32Hash> slot;
+    // which slot and table each key has, the free lists, the pins of staged batches (guarded by
+    // mu) and the hold of in-flight calls (keycache_alloc.h)
+    nwv::KeyAlloc alloc;
+    nwv::KeyHold hold;
     DevBuf recs;  // cap x KC_SLOT_WORDS words
-    uint32_t used = 0, cap = 0;
+    uint32_t cap = 0;
     bool broken = false;  // allocation or fill failed once: stay uncached
     bool b_ready = false;  // slot 0 (B) filled
     // registered keys' fixed-base comb tables (k_key_comb_fill, COMB_WORDS words each; allocated
-    // once at full size, NWV_COMB_KEYS tables, default 1,024 = 64 MiB); comb_of[slot] = table
+    // once at full size, NWV_COMB_KEYS tables, default 1,024 = 64 MiB); alloc.table_of(slot)
     DevBuf combs;
-    uint32_t comb_cap = 0, comb_used = 0;
-    std::vector<uint32_t> comb_of;
-    uint64_t reg_fp = 0;  // fingerprint of the last key list registered with every key combed
+    uint32_t comb_cap = 0;
 };
 
 // One device of a context: the basepoint table, the key cache and the pool of lanes (created on
@@ -257,7 +245,9 @@ struct Gpu {
     uint32_t flags = 0;
     DevBuf btab;
     DevBuf comb;  // fixed-base comb table of the MSM's basepoint term (msm.h)
-    KeyCache kc;
+    // (shared: a staged batch unpins its slots when it is freed, which may be after the context)
+    std::shared_ptr<KeyCache> kcp = std::make_shared<KeyCache>();
+    KeyCache& kc = *kcp;
     std::mutex mu;  // guards the pool
     std::condition_variable cv;
     std::vector<Lane*> lanes, idle;
@@ -275,6 +265,35 @@ struct Gpu {
 int with_device(Lane& d) {
     NWV_HIP(hipSetDevice(d.ordinal));
     return NWV_OK;
+}
+
+// The hold of a call on its device's key cache.  Every call that obtains slot or table indices
+// takes it shared before it looks them up and keeps it until its kernels have finished on the
+// lane's stream (in practice: until the lane goes back to the pool), so nwv_keycache_retain,
+// which holds it exclusive, never frees an index that a running kernel reads.  Taken before
+// KeyCache::mu, never while holding it.
+void kc_hold_shared(Lane& d) {
+    if (d.kc_held != Lane::KC_NONE) return;
+    d.gpu->kc.hold.lock_shared();
+    d.kc_held = Lane::KC_SHARED;
+    d.kc_unsynced = true;
+}
+void kc_hold_excl(Lane& d) {
+    if (d.kc_held != Lane::KC_NONE) return;
+    d.gpu->kc.hold.lock();
+    d.kc_held = Lane::KC_EXCL;
+    d.kc_unsynced = true;
+}
+// the call has synchronised its stream after its last kernel: the release need not wait again
+void kc_call_done(Lane& d) { d.kc_unsynced = false; }
+void kc_hold_release(Lane& d) {
+    if (d.kc_held == Lane::KC_NONE) return;
+    // (an error return may have left work queued that still reads the cache)
+    if (d.kc_unsynced && d.stream) (void)hipStreamSynchronize(d.stream);
+    if (d.kc_held == Lane::KC_EXCL) d.gpu->kc.hold.unlock();
+    else d.gpu->kc.hold.unlock_shared();
+    d.kc_held = Lane::KC_NONE;
+    d.kc_unsynced = false;
 }
 
 void lane_close(Lane& d) {
@@ -366,6 +385,7 @@ class LaneRef {
     }
     ~LaneRef() {
         if (!lane_) return;
+        kc_hold_release(*lane_);
         {
             std::lock_guard<std::mutex> lk(g_.mu);
             g_.idle.push_back(lane_);
@@ -1137,6 +1157,7 @@ int keycache_slots(Lane& d, const uint8_t* keys, size_t m, std::vector<uint32_t>
     }();
     if (m == 0 || (d.flags & NWV_FLAG_NO_KEYCACHE) || (long)m > max_keys) return NWV_OK;
     KeyCache& kc = d.gpu->kc;
+    kc_hold_shared(d);  // the indices are read by this call's kernels: held until the lane is returned
     std::lock_guard<std::mutex> g(kc.mu);
     if (kc.broken) return NWV_OK;
     if (lookup_only) {
@@ -1145,12 +1166,12 @@ int keycache_slots(Lane& d, const uint8_t* keys, size_t m, std::vector<uint32_t>
         for (size_t j = 0; j < m; j++) {
             Key32 k;
             std::memcpy(k.b, keys + 32 * j, 32);
-            auto it = kc.slot.find(k);
-            if (it == kc.slot.end()) {
+            const uint32_t sl = kc.alloc.find(k);
+            if (sl == nwv::KeyAlloc::NONE) {
                 out.clear();
                 return NWV_OK;
             }
-            out[j] = it->second;
+            out[j] = sl;
         }
         return NWV_OK;
     }
@@ -1162,7 +1183,7 @@ int keycache_slots(Lane& d, const uint8_t* keys, size_t m, std::vector<uint32_t>
             return NWV_OK;
         }
         kc.cap = kCap;
-        kc.used = 1;  // slot 0: B (filled with the first misses below)
+        kc.alloc.init_slots(kCap);  // slot 0: B (filled with the first misses below)
     }
     out.resize(m);
     thread_local std::vector<uint8_t> miss_keys;
@@ -1176,13 +1197,17 @@ int keycache_slots(Lane& d, const uint8_t* keys, size_t m, std::vector<uint32_t>
         miss_slots.push_back(0);
     }
     std::vector<Key32> fresh;
-    uint32_t next = kc.used;
+    // slots taken below are unpublished (a freed slot first, then a never-used one): given back if
+    // the call goes uncached, published only once their records are written
+    auto give_back = [&] {
+        for (size_t f = 0; f < fresh.size(); f++) kc.alloc.give_back_slot(miss_slots[miss_slots.size() - fresh.size() + f]);
+    };
     for (size_t j = 0; j < m; j++) {
         Key32 k;
         std::memcpy(k.b, keys + 32 * j, 32);
-        auto it = kc.slot.find(k);
-        if (it != kc.slot.end()) {
-            out[j] = it->second;
+        const uint32_t have = kc.alloc.find(k);
+        if (have != nwv::KeyAlloc::NONE) {
+            out[j] = have;
             continue;
         }
         // a key repeated inside one call gets one slot (keys are distinct per call, but be safe)
@@ -1193,20 +1218,23 @@ int keycache_slots(Lane& d, const uint8_t* keys, size_t m, std::vector<uint32_t>
                 dup = true;
             }
         if (dup) continue;
-        if (next >= kc.cap) {  // full: this call goes uncached, nothing is published
+        const uint32_t next = kc.alloc.take_slot();
+        if (next == nwv::KeyAlloc::NONE) {  // full: this call goes uncached, nothing is published
+            give_back();
             out.clear();
             return NWV_OK;
         }
         fresh.push_back(k);
         miss_keys.insert(miss_keys.end(), keys + 32 * j, keys + 32 * j + 32);
         miss_slots.push_back(next);
-        out[j] = next++;
+        out[j] = next;
     }
     if (!miss_slots.empty()) {
         const size_t cnt = miss_slots.size();
         DevBuf tmp;
         auto fail = [&](int rc) {
             tmp.release();
+            give_back();
             kc.broken = true;
             out.clear();
             return rc;
@@ -1222,11 +1250,16 @@ int keycache_slots(Lane& d, const uint8_t* keys, size_t m, std::vector<uint32_t>
         if (hipGetLastError() != hipSuccess || hipStreamSynchronize(d.stream) != hipSuccess)
             return fail(set_err(NWV_ERR_HIP, "key cache fill"));
         tmp.release();
-        for (size_t f = 0; f < fresh.size(); f++) kc.slot.emplace(fresh[f], miss_slots[miss_slots.size() - fresh.size() + f]);
+        for (size_t f = 0; f < fresh.size(); f++) kc.alloc.publish(fresh[f], miss_slots[miss_slots.size() - fresh.size() + f]);
         kc.b_ready = true;
-        kc.used = next;
     }
     return NWV_OK;
+}
+
+void kc_unpin(KeyCache& kc, std::vector<uint32_t>& slots) {
+    std::lock_guard<std::mutex> g(kc.mu);
+    for (uint32_t sl : slots) kc.alloc.unpin(sl);
+    slots.clear();
 }
 
 // Keyed staging: signature i of [lo, hi) is by keys[key_idx[i]].  The distinct keys that occur
@@ -1235,7 +1268,8 @@ int keycache_slots(Lane& d, const uint8_t* keys, size_t m, std::vector<uint32_t>
 int ed_stage_keyed(Lane& d, EdBuffers& b, size_t lo, size_t hi, size_t n_keys, const uint8_t* keys,
                    const uint32_t* key_idx, const uint8_t* sig, const uint8_t* msg_base,
                    const uint64_t* msg_off, const uint32_t* msg_len, const uint8_t* seed32,
-                   const DevBuf* dev_msg = nullptr, bool kc_lookup_only = false, size_t comb_max = 0) {
+                   const DevBuf* dev_msg = nullptr, bool kc_lookup_only = false, size_t comb_max = 0,
+                   std::vector<uint32_t>* pin_out = nullptr) {
     const size_t n = hi - lo;
     // per-thread scratch reused across calls (fresh large vectors are page-faulted in every call)
     thread_local std::vector<uint32_t> local, cnt, kid, koff, ksig, cur;
@@ -1266,6 +1300,14 @@ int ed_stage_keyed(Lane& d, EdBuffers& b, size_t lo, size_t hi, size_t n_keys, c
     thread_local std::vector<uint32_t> kslot;
     int rc = keycache_slots(d, klist.data(), m, kslot, kc_lookup_only);
     if (rc) return rc;
+    if (pin_out && !kslot.empty()) {
+        // a staged batch reads these slots on every replay: pinned (under the call's hold, so no
+        // retain runs in between) until kc_unpin at nwv_staged_free
+        KeyCache& kc = d.gpu->kc;
+        std::lock_guard<std::mutex> g(kc.mu);
+        for (uint32_t sl : kslot) kc.alloc.pin(sl);
+        *pin_out = kslot;
+    }
     KeyedTail kt{klist.data(), m, koff.data(), ksig.data(), kslot.empty() ? nullptr : kslot.data()};
     // the comb path (k_ed_comb): above TINY_MAX and at most comb_max signatures (0: the caller does
     // not offer it), every key registered (comb table present), no flag that forces a path
@@ -1274,12 +1316,12 @@ int ed_stage_keyed(Lane& d, EdBuffers& b, size_t lo, size_t hi, size_t n_keys, c
         !(d.flags & (NWV_FLAG_NO_TINY | NWV_FLAG_MSM_ALWAYS | NWV_FLAG_MSM_NEVER))) {
         KeyCache& kc = d.gpu->kc;
         std::lock_guard<std::mutex> g(kc.mu);
-        bool all = !kc.comb_of.empty();
+        bool all = kc.comb_cap != 0;
         sig_slot.resize(n);
         sig_cidx.resize(n);
         for (size_t i = 0; i < n && all; i++) {
             const uint32_t sl = kslot[kid[i]];
-            const uint32_t c = sl < kc.comb_of.size() ? kc.comb_of[sl] : UINT32_MAX;
+            const uint32_t c = kc.alloc.table_of(sl);
             all = c != UINT32_MAX && sl < kc.cap && c < kc.comb_cap;
             sig_slot[i] = sl;
             sig_cidx[i] = c;
@@ -1295,10 +1337,10 @@ int ed_stage_keyed(Lane& d, EdBuffers& b, size_t lo, size_t hi, size_t n_keys, c
     if (n && n <= (size_t)TINY_MAX && !kslot.empty() && !(d.flags & (NWV_FLAG_NO_TINY | NWV_FLAG_MSM_NEVER))) {
         KeyCache& kc = d.gpu->kc;
         std::lock_guard<std::mutex> g(kc.mu);
-        bool all = !kc.comb_of.empty();
+        bool all = kc.comb_cap != 0;
         for (size_t i = 0; i < n && all; i++) {
             const uint32_t sl = kslot[kid[i]];
-            const uint32_t c = sl < kc.comb_of.size() ? kc.comb_of[sl] : UINT32_MAX;
+            const uint32_t c = kc.alloc.table_of(sl);
             all = c != UINT32_MAX;
             b.tiny_slot[i] = sl;
             b.tiny_cidx[i] = c;
@@ -1388,6 +1430,10 @@ struct nwv_staged {
     size_t dev_index = 0;
     std::shared_ptr<nwv::PlaceTable> place;  // (a batch may outlive its context)
     nwv::Ticket load;
+    // a keyed batch over the key cache: the slots its graph reads, pinned from staging until
+    // nwv_staged_free (nwv_keycache_retain leaves them alone)
+    std::shared_ptr<KeyCache> kcp;
+    std::vector<uint32_t> pinned;
 };
 
 // Shard [0, n) into contiguous, 64-aligned ranges of at least ctx->shard_min signatures over the
@@ -1517,9 +1563,10 @@ int nwv_keycache_stats(const nwv_ctx* ctx, int device_index, uint64_t out[4]) {
     if (device_index < 0 || device_index >= (int)ctx->devs.size()) return set_err(NWV_ERR_ARG, "bad device index");
     KeyCache& kc = ctx->devs[device_index]->kc;
     std::lock_guard<std::mutex> g(kc.mu);
-    out[0] = kc.b_ready ? kc.used : 0;  // used is 1 from allocation on; slot 0 is filled with the first misses
+    // the live counts (slot 0 is counted from allocation on, and filled with the first misses)
+    out[0] = kc.b_ready ? kc.alloc.slots_live() : 0;
     out[1] = kc.cap;
-    out[2] = kc.comb_used;
+    out[2] = kc.alloc.tables_live();
     out[3] = kc.comb_cap;
     return 4;
 }
@@ -1974,6 +2021,7 @@ static int verify_batch_keyed_impl(nwv_ctx* ctx, size_t n_keys, const uint8_t* k
         r = batch_on_device(d, d.ed, hi - lo, s2, d.stream, &ok,
                             verdict_bits_or_null ? verdict_bits_or_null + lo / 64 : nullptr, true);
         if (r) return r;
+        kc_call_done(d);  // every path of batch_on_device ends with the stream synchronised
         std::lock_guard<std::mutex> g(omu);
         if (!ok) *all_valid = 0;
         return NWV_OK;
@@ -2005,43 +2053,74 @@ int nwv_keycache_register(nwv_ctx* ctx, size_t n_keys, const uint8_t* keys) {
     if (fp == 0) fp = 1;
     static const uint32_t comb_keys = (uint32_t)env_size("NWV_COMB_KEYS", 1024, 0, 1u << 16);
     for (Gpu* g : ctx->devs) {
+        if (g->flags & NWV_FLAG_NO_KEYCACHE) continue;
         {
-            std::lock_guard<std::mutex> lk(g->kc.mu);
-            if (g->kc.reg_fp == fp) continue;
+            // nothing to fill (the same list again, or every key has its slot and the tables are
+            // used up): in-flight calls are not made to drain for it
+            KeyCache& kc = g->kc;
+            std::lock_guard<std::mutex> lk(kc.mu);
+            if (kc.alloc.reg_fp() == fp || kc.broken) continue;
+            bool work = !kc.cap || !kc.b_ready;
+            const bool tables = comb_keys && (!kc.comb_cap || kc.alloc.table_available());
+            for (size_t j = 0; j < n_keys && !work; j++) {
+                Key32 k;
+                std::memcpy(k.b, keys + 32 * j, 32);
+                const uint32_t sl = kc.alloc.find(k);
+                work = sl == nwv::KeyAlloc::NONE ? kc.alloc.slot_available()
+                                                 : tables && kc.alloc.table_of(sl) == nwv::KeyAlloc::NONE;
+            }
+            if (!work) continue;
         }
         LaneRef lane(*g);
         int rc = lane.rc();
+        if (rc) return rc;
+        // the filling part holds the cache exclusive: it waits for the calls in flight on this
+        // device, and new ones wait for it (released with the lane)
+        kc_hold_excl(*lane);
         std::vector<uint32_t> slots, all;
         for (size_t a = 0; a < n_keys && !rc; a += 4096) {
             rc = keycache_slots(*lane, keys + 32 * a, std::min<size_t>(4096, n_keys - a), slots);
             all.insert(all.end(), slots.begin(), slots.end());
         }
         if (rc) return rc;
-        if (all.size() != n_keys || comb_keys == 0 || (g->flags & NWV_FLAG_NO_KEYCACHE)) continue;  // uncached
+        kc_call_done(*lane);  // (a fill is synchronised before it publishes)
+        if (all.size() != n_keys || comb_keys == 0) continue;  // uncached
         // fixed-base comb tables for the keys that have none yet (the one-launch path, k_ed_tiny)
         KeyCache& kc = g->kc;
         std::lock_guard<std::mutex> lk(kc.mu);
         if (!kc.comb_cap) {
             if (kc.combs.ensure((size_t)4 * COMB_WORDS * comb_keys)) continue;  // no room: batches use the MSM
             kc.comb_cap = comb_keys;
-            kc.comb_of.assign(kc.cap ? kc.cap : (1u << 16), UINT32_MAX);
+            kc.alloc.init_tables(comb_keys);
         }
         std::vector<uint8_t> nk;
         std::vector<uint32_t> ni, nslot;
         for (size_t j = 0; j < n_keys; j++) {
             const uint32_t sl = all[j];
-            if (sl >= kc.comb_of.size() || kc.comb_of[sl] != UINT32_MAX) continue;
+            if (sl >= kc.cap || kc.alloc.table_of(sl) != nwv::KeyAlloc::NONE) continue;
             bool dup = false;
             for (uint32_t q : nslot) dup = dup || q == sl;
             if (dup) continue;
-            if (kc.comb_used + ni.size() >= kc.comb_cap) break;  // full: later keys take the MSM path
+            // an unpublished table: a freed one first, then a never-used one
+            const uint32_t t = kc.alloc.take_table();
+            if (t == nwv::KeyAlloc::NONE) break;  // full: later keys take the MSM path
             nk.insert(nk.end(), keys + 32 * j, keys + 32 * j + 32);
-            ni.push_back(kc.comb_used + (uint32_t)ni.size());
+            ni.push_back(t);
             nslot.push_back(sl);
         }
         if (!ni.empty()) {
             Lane& d = *lane;
             DevBuf tmp;
+            // (taken tables go back on every error return below: none is published before the sync)
+            struct Undo {
+                KeyCache& kc;
+                std::vector<uint32_t>& ni;
+                bool armed = true;
+                ~Undo() {
+                    if (armed)
+                        for (uint32_t t : ni) kc.alloc.give_back_table(t);
+                }
+            } undo{kc, ni};
             if ((rc = tmp.ensure(36 * ni.size() + 64))) return rc;
             uint8_t* tk = tmp.as<uint8_t>();
             uint32_t* ti = reinterpret_cast<uint32_t*>(tk + 32 * ni.size());
@@ -2052,13 +2131,38 @@ int nwv_keycache_register(nwv_ctx* ctx, size_t n_keys, const uint8_t* keys) {
                                (uint32_t)ni.size(), tk, ti, kc.combs.as<uint32_t>());
             NWV_HIP(hipGetLastError());
             NWV_HIP(hipStreamSynchronize(d.stream));  // published only once the tables are written
-            for (size_t q = 0; q < ni.size(); q++) kc.comb_of[nslot[q]] = ni[q];
-            kc.comb_used += (uint32_t)ni.size();
+            undo.armed = false;
+            tmp.release();
+            for (size_t q = 0; q < ni.size(); q++) kc.alloc.set_table(nslot[q], ni[q]);
         }
         bool every = true;
-        for (size_t j = 0; j < n_keys && every; j++) every = all[j] < kc.comb_of.size() && kc.comb_of[all[j]] != UINT32_MAX;
-        if (every) kc.reg_fp = fp;
+        for (size_t j = 0; j < n_keys && every; j++) every = kc.alloc.table_of(all[j]) != nwv::KeyAlloc::NONE;
+        if (every) kc.alloc.set_registered(fp, all.data(), all.size());
     }
+    return NWV_OK;
+}
+
+// Epoch change (Core::change_epoch): on every device, give back the slot and comb table of every
+// cached key that the new committee does not name.  No kernel runs: the exclusive hold waits for
+// the calls in flight on the device, the pins of staged batches are respected, and a freed index
+// is rewritten only by a later fill, which publishes its key after the write has finished.
+int nwv_keycache_retain(nwv_ctx* ctx, size_t n_keys, const uint8_t* keys, uint64_t* out_or_null) {
+    if (!ctx || (n_keys && !keys)) return set_err(NWV_ERR_ARG, "null argument");
+    uint64_t sum[4] = {0, 0, 0, 0};
+    for (Gpu* g : ctx->devs) {
+        if (g->flags & NWV_FLAG_NO_KEYCACHE) continue;
+        KeyCache& kc = g->kc;
+        kc.hold.lock();
+        {
+            std::lock_guard<std::mutex> lk(kc.mu);
+            uint64_t r[3];
+            kc.alloc.retain(keys, n_keys, r);
+            for (int k = 0; k < 3; k++) sum[k] += r[k];
+            sum[3] += kc.b_ready ? kc.alloc.slots_live() : 0;
+        }
+        kc.hold.unlock();
+    }
+    if (out_or_null) std::memcpy(out_or_null, sum, sizeof sum);
     return NWV_OK;
 }
 
@@ -2180,6 +2284,7 @@ static int staged_create(nwv_ctx* ctx, int device_index, size_t n, nwv_staged** 
         rc = lane.rc();
         if (!rc) rc = stage(*lane, st->buf);
         if (!rc && hipStreamSynchronize((*lane).stream) != hipSuccess) rc = set_err(NWV_ERR_HIP, "stage sync");
+        if (!rc) kc_call_done(*lane);
     }
     Lane& o = st->own;
     o.gpu = st->gpu;
@@ -2218,9 +2323,19 @@ int nwv_stage_ed25519_keyed(nwv_ctx* ctx, int device_index, size_t n_keys, const
                             const uint32_t* key_idx, const uint8_t* sig, const uint8_t* msg_base,
                             const uint64_t* msg_off, const uint32_t* msg_len, nwv_staged** out) {
     if (n && (!keys || !key_idx || !sig || !msg_off || !msg_len)) return set_err(NWV_ERR_ARG, "null argument");
-    return staged_create(ctx, device_index, n, out, [&](Lane& d, EdBuffers& b) {
-        return ed_stage_keyed(d, b, 0, n, n_keys, keys, key_idx, sig, msg_base, msg_off, msg_len, nullptr);
+    std::vector<uint32_t> pinned;
+    const int rc = staged_create(ctx, device_index, n, out, [&](Lane& d, EdBuffers& b) {
+        return ed_stage_keyed(d, b, 0, n, n_keys, keys, key_idx, sig, msg_base, msg_off, msg_len, nullptr, nullptr, false,
+                              0, &pinned);
     });
+    if (pinned.empty()) return rc;
+    if (rc) {
+        kc_unpin(ctx->devs[device_index]->kc, pinned);
+        return rc;
+    }
+    (*out)->kcp = ctx->devs[device_index]->kcp;
+    (*out)->pinned.swap(pinned);
+    return rc;
 }
 
 static int staged_collect_times(nwv_staged* st) {
@@ -2506,6 +2621,7 @@ void nwv_staged_free(nwv_staged* st) {
         (void)hipSetDevice(st->own.ordinal);
         if (st->stream) (void)hipStreamSynchronize(st->stream);
         st->load.release();
+        if (st->kcp) kc_unpin(*st->kcp, st->pinned);  // (after the sync: no replay reads them now)
         if (st->graph) (void)hipGraphExecDestroy(st->graph);
         for (auto& e : st->seed_ev)
             if (e) (void)hipEventDestroy(e);
@@ -2688,6 +2804,7 @@ int nwv_ed25519_verify_batch_keyed_digests(nwv_ctx* ctx, size_t n_pre, const uin
     if (rc) return rc;
     if (!ok) *all_valid = 0;
     NWV_HIP(hipStreamSynchronize(d.stream));  // already synchronised by the verdict read
+    kc_call_done(d);
     std::memcpy(digests_out, d.b2dig.p, 32 * n_pre);
     return NWV_OK;
 }

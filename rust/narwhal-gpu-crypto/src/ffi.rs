@@ -250,6 +250,8 @@ extern "C" {
     ) -> c_int;
     // committee key cache (include/nwv.h): fill it with the committee's keys at epoch start
     pub fn nwv_keycache_register(ctx: *mut NwvCtx, n_keys: usize, keys: *const u8) -> c_int;
+    // epoch change: retire every cached key that is not in keys (n_keys = 0, null: all); out_or_null[4]
+    pub fn nwv_keycache_retain(ctx: *mut NwvCtx, n_keys: usize, keys: *const u8, out_or_null: *mut u64) -> c_int;
     // diagnostics: slots used, slot capacity, comb tables used, comb-table capacity of one device's cache
     pub fn nwv_keycache_stats(ctx: *const NwvCtx, device_index: c_int, out: *mut u64) -> c_int;
     // ---- fastcrypto trait surface: Verifier::verify, VerifyingKey::verify_batch_empty_fail, AggregateAuthenticator::{verify, batch_verify} (include/nwv.h)

@@ -382,6 +382,36 @@ impl AggregateAuthenticator for GpuEd25519AggregateSignature {
     }
 }
 
+// ------------------------------------------------------------------------ epoch change --
+/// What `keycache_retain` did, summed over the devices.
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct KeycacheRetained {
+    pub slots_retired: u64,
+    pub combs_retired: u64,
+    /// slots kept only because a live staged batch reads them
+    pub pinned_kept: u64,
+    /// slots in use after the call (the basepoint's included)
+    pub used: u64,
+}
+
+/// `Core::change_epoch` (primary/src/core.rs:592-611): retire every cached Ed25519 key that the
+/// new committee does not name, so its slot and comb table serve later keys; validators that stay
+/// keep theirs.  Registers nothing: the new committee is registered by the next call that names it.
+pub fn keycache_retain<K: AsRef<[u8]>>(new_committee: &[K]) -> Result<KeycacheRetained, String> {
+    if new_committee.iter().any(|k| k.as_ref().len() != PUBLIC_KEY_LENGTH) {
+        return Err("a key is not 32 bytes".into());
+    }
+    let keys = flat(new_committee.iter());
+    let mut out = [0u64; 4];
+    let p = if new_committee.is_empty() { std::ptr::null() } else { keys.as_ptr() };
+    let rc = unsafe { ffi::nwv_keycache_retain(ctx(), new_committee.len(), p, out.as_mut_ptr()) };
+    if rc == ffi::NWV_OK {
+        Ok(KeycacheRetained { slots_retired: out[0], combs_retired: out[1], pinned_kept: out[2], used: out[3] })
+    } else {
+        Err(last_error())
+    }
+}
+
 // ------------------------------------------------------------------- worker digests --
 /// `Batch::digest` (types/src/primary.rs:65-73) of many batches in one GPU call: `batches[i]` is
 /// the concatenation of batch i's transactions.
