@@ -41,7 +41,11 @@ oracle:
 
 hostemu: tests/_build/libhostemu.so tests/_build/libsvcstub.so tests/_build/libblsemu.so tests/_build/libblsshard.so \
 	tests/_build/libcombemu.so tests/_build/libfeseeded.so tests/_build/libtrimemu.so tests/_build/libfoldemu.so \
-	tests/_build/libplace.so tests/_build/libkcalloc.so
+	tests/_build/libplace.so tests/_build/libkcalloc.so tests/_build/libgroupkeys.so
+# the trait surface's grouping of a batch's keys (group_keys.h) with no HIP (tests/test_group_keys_host.py)
+tests/_build/libgroupkeys.so: tests/hostemu/group_keys_stub.cpp narwhal_amd/csrc/group_keys.h
+	@mkdir -p tests/_build
+	g++ -O2 -g -std=c++17 -fPIC -shared -pthread -o $@ tests/hostemu/group_keys_stub.cpp
 # the key cache's slot / table bookkeeping and its hold (keycache_alloc.h) with no HIP
 # (tests/test_keycache_alloc_host.py)
 tests/_build/libkcalloc.so: tests/hostemu/keycache_alloc_stub.cpp narwhal_amd/csrc/keycache_alloc.h

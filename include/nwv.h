@@ -180,6 +180,32 @@ int nwv_ed25519_verify_batch_keyed(nwv_ctx* ctx, size_t n_keys, const uint8_t* k
                                    const uint32_t* key_idx, const uint8_t* sig, const uint8_t* msg_base,
                                    const uint64_t* msg_off, const uint32_t* msg_len,
                                    const uint8_t seed32[32], int* all_valid, uint64_t* verdict_bits_or_null);
+/* Batch verification that finds the repeated keys itself: the arguments, return codes, *all_valid
+ * and verdict bits of nwv_ed25519_verify_batch for every input; only the path differs.  This is
+ * what the trait-surface calls below run on (they name one key per signature).  The keys are
+ * grouped by their 32 bytes on the host -- byte equality, as ed25519_consensus groups by
+ * VerificationKeyBytes: two encodings of one point are two keys -- and the call then runs, per
+ * range, on the device that serves it:
+ *   - every distinct key in that device's key cache: keyed over the cache, so a registered
+ *     committee's certificate takes the one-launch path (at most 64 signatures) or the comb kernel
+ *     (at most nwv_comb_batch_max), under the conditions of nwv_keycache_register;
+ *   - some key not cached, at most n / 2 distinct keys: keyed and uncached (one MSM point per key);
+ *   - some key not cached, more distinct keys: exactly as nwv_ed25519_verify_batch.
+ * The cache is only looked up: the call never takes a slot and never waits for a fill, so stray
+ * keys cannot displace a committee.  The coefficient z_i belongs to the caller's signature i
+ * whatever the grouping.  A context opened with NWV_FLAG_MSM_NEVER, and a call of more than
+ * NWV_GROUP_MAX_N signatures (env, read once; default 16,384, the shard minimum, so a grouped call
+ * is one range and the host pass is bounded), is passed to nwv_ed25519_verify_batch as it is. */
+int nwv_ed25519_verify_batch_grouped(nwv_ctx* ctx, size_t n, const uint8_t* pk, const uint8_t* sig,
+                                     const uint8_t* msg_base, const uint64_t* msg_off,
+                                     const uint32_t* msg_len, const uint8_t seed32[32],
+                                     int* all_valid, uint64_t* verdict_bits_or_null);
+/* Diagnostics: the context's grouped calls so far (n = 0 and argument errors do not count):
+ * out[0] calls, out[1] calls that ran with every key from the cache, out[2] calls that ran keyed
+ * and uncached, out[3] calls that ran un-keyed (the two pass-through cases included).  A call of
+ * several ranges counts once, as its least keyed range; a call that failed counts in out[0] only.
+ * Returns NWV_OK or NWV_ERR_ARG. */
+int nwv_diag_grouped(const nwv_ctx* ctx, uint64_t out[4]);
 /* Digest-then-verify: the n_pre preimages are hashed with BLAKE2b-256 on the
  * device (digests_out receives them, n_pre x 32) and signature i is checked over the 32-byte
  * digest digest_idx[i] straight from device memory, with no host round trip between the hash and
@@ -231,6 +257,9 @@ int nwv_keycache_stats(const nwv_ctx* ctx, int device_index, uint64_t out[4]);
 
 /* ---- fastcrypto 0.1.2 trait surface (Ed25519 scheme module; contract of
  *      crypto/src/bls12377/mod.rs:264-291 and :485-577) ---- */
+/* The three batch calls below run on nwv_ed25519_verify_batch_grouped: with the committee
+ * registered (nwv_keycache_register, once at start-up and at every epoch change) they reach the
+ * cached, one-launch and comb paths with no other change at the call sites. */
 /* Verifier::verify(&self, msg, sig): NWV_OK or NWV_ERR_SIGNATURE */
 int nwv_ed25519_pubkey_verify(nwv_ctx* ctx, const uint8_t pk[32], const uint8_t* msg,
                               size_t msg_len, const uint8_t sig[64]);

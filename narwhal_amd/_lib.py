@@ -74,6 +74,8 @@ def load():
         "nwv_last_error": ([], ctypes.c_char_p),
         "nwv_ed25519_verify_each": ([_vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp], _i32),
         "nwv_ed25519_verify_batch": ([_vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp], _i32),
+        "nwv_ed25519_verify_batch_grouped": ([_vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp], _i32),
+        "nwv_diag_grouped": ([_vp, _vp], _i32),
         "nwv_ed25519_pubkey_verify": ([_vp, _vp, _vp, _sz, _vp], _i32),
         "nwv_keycache_register": ([_vp, _sz, _vp], _i32),
         "nwv_keycache_stats": ([_vp, _i32, _vp], _i32),
@@ -295,6 +297,26 @@ class Engine:
                                                  _ptr(offs), _ptr(lens), _seed(seed), ctypes.byref(allv),
                                                  _ptr(bits) if want_bits else None))
         return bool(allv.value), (list(unpack_bits(bits, n)) if want_bits else None)
+
+    def verify_batch_grouped_arrays(self, pk, sig, arena, offs, lens, seed=None, want_bits=True):
+        """nwv_ed25519_verify_batch_grouped (what the trait-surface calls run on): pk uint8 [n*32],
+        sig uint8 [n*64], one key per signature; the library groups equal keys and uses the key
+        cache when every key is in it -> (all_valid, bool array of verdicts or None)"""
+        n = len(offs)
+        bits = np.zeros((n + 63) // 64 + 1, dtype=np.uint64)
+        allv = _i32(0)
+        _check(self.lib.nwv_ed25519_verify_batch_grouped(self._h, n, _ptr(pk), _ptr(sig), _ptr(arena), _ptr(offs),
+                                                         _ptr(lens), _seed(seed), ctypes.byref(allv),
+                                                         _ptr(bits) if want_bits else None))
+        return bool(allv.value), (unpack_bits(bits, n) if want_bits else None)
+
+    def diag_grouped(self):
+        """nwv_diag_grouped: {'calls': grouped calls, 'cached': ran with every key from the cache,
+        'keyed': ran keyed and uncached, 'unkeyed': ran as verify_batch (pass-through included)}"""
+        names = ("calls", "cached", "keyed", "unkeyed")
+        out = np.zeros(len(names), dtype=np.uint64)
+        _check(self.lib.nwv_diag_grouped(self._h, out.ctypes.data))
+        return {nm: int(v) for nm, v in zip(names, out)}
 
     def verify_batch_keyed(self, keys, key_idx, sigs, msgs, seed=None, want_bits=True):
         """keys: list of distinct 32-byte keys; key_idx[i]: key of signature i; sigs, msgs: per

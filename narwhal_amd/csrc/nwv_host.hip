@@ -26,6 +26,7 @@
 #include "msm_kernels.hip"
 #include "tiny_kernels.hip"
 #include "comb_kernels.hip"
+#include "group_keys.h"
 #include "keycache_alloc.h"
 #include "place.h"
 #include "shard.h"
@@ -1256,6 +1257,22 @@ int keycache_slots(Lane& d, const uint8_t* keys, size_t m, std::vector<uint32_t>
     return NWV_OK;
 }
 
+// Whether each of m keys has a slot on d's device now.  Only looks: no hold is taken and no index
+// is kept, so the answer may be stale by the time a staging looks the keys up again (the grouped
+// call uses it to choose a form, never for correctness).  Stops at the first miss.
+bool keycache_has_all(Lane& d, const uint8_t* keys, size_t m) {
+    if (d.flags & NWV_FLAG_NO_KEYCACHE) return false;
+    KeyCache& kc = d.gpu->kc;
+    std::lock_guard<std::mutex> g(kc.mu);
+    if (kc.broken || !kc.cap || !kc.b_ready) return false;
+    for (size_t j = 0; j < m; j++) {
+        Key32 k;
+        std::memcpy(k.b, keys + 32 * j, 32);
+        if (kc.alloc.find(k) == nwv::KeyAlloc::NONE) return false;
+    }
+    return true;
+}
+
 void kc_unpin(KeyCache& kc, std::vector<uint32_t>& slots) {
     std::lock_guard<std::mutex> g(kc.mu);
     for (uint32_t sl : slots) kc.alloc.unpin(sl);
@@ -1382,6 +1399,9 @@ struct nwv_ctx {
     // the load of every device object, by which calls are placed (place.h; env NWV_PLACE, read at
     // nwv_init); the BLS12-381 engine shares it when it has as many device objects
     std::shared_ptr<nwv::PlaceTable> place;
+    // nwv_ed25519_verify_batch_grouped (the trait surface): calls, and how each one ran -- every
+    // key from the cache, keyed and uncached, un-keyed (nwv_diag_grouped)
+    std::atomic<uint64_t> n_grouped[4] = {};
 };
 
 // Per-kernel device time of the staged pipelines (HIP events on the batch's own stream).
@@ -2036,6 +2056,85 @@ int nwv_ed25519_verify_batch_keyed(nwv_ctx* ctx, size_t n_keys, const uint8_t* k
                                    verdict_bits_or_null, false);
 }
 
+// The trait surface's batches (one key per signature, nothing said about repeats): group the keys
+// by their bytes (group_keys.h), as ed25519-consensus' batch::Verifier does, and run keyed with a
+// lookup-only cache probe.  The form is chosen per range, on the lane that serves it:
+//   every distinct key in that device's cache  -> keyed over the cache (k_ed_tiny / k_ed_comb under
+//                                                 ed_stage_keyed's conditions, else the 128-bit MSM)
+//   a miss, at most n / 2 distinct keys        -> keyed and uncached (one MSM point per key)
+//   a miss, more distinct keys                 -> the un-keyed staging of nwv_ed25519_verify_batch
+// The call never takes a cache slot and never waits for a fill.  z_i stays indexed by the
+// caller's signature index: grouping only says which signatures share a point.
+// The pass is bounded: a range whose first key is not cached cannot run from the cache, so its
+// grouping stops at the first distinct key past n / 2 (a batch of strangers pays for half a pass).
+static size_t group_max_n() {
+    static const size_t v = env_size("NWV_GROUP_MAX_N", 16384, 0, SIZE_MAX);
+    return v;
+}
+
+int nwv_ed25519_verify_batch_grouped(nwv_ctx* ctx, size_t n, const uint8_t* pk, const uint8_t* sig,
+                                     const uint8_t* msg_base, const uint64_t* msg_off,
+                                     const uint32_t* msg_len, const uint8_t seed32[32], int* all_valid,
+                                     uint64_t* verdict_bits_or_null) {
+    if (!ctx || !all_valid || (n && (!pk || !sig || !msg_off || !msg_len)))
+        return set_err(NWV_ERR_ARG, "null argument");
+    *all_valid = 1;
+    if (n == 0) return NWV_OK;
+    ctx->n_grouped[0]++;
+    if (n > group_max_n() || ctx->devs.empty() || (ctx->devs[0]->flags & NWV_FLAG_MSM_NEVER)) {
+        ctx->n_grouped[3]++;
+        return nwv_ed25519_verify_batch(ctx, n, pk, sig, msg_base, msg_off, msg_len, seed32, all_valid,
+                                        verdict_bits_or_null);
+    }
+    for (size_t i = 0; i < n && !msg_base; i++)
+        if (msg_len[i]) return set_err(NWV_ERR_ARG, "null msg_base");
+    uint8_t seed[32];
+    fill_seed(seed32, seed);
+    std::mutex omu;
+    const size_t comb_max =
+        nwv::ed_shard_ranges(n, ctx->devs.size(), ctx->shard_min).size() == 1 ? ctx->comb_batch_max.load() : 0;
+    int how_call = 1;  // the call counts as its least keyed range: 1 cached, 2 keyed uncached, 3 un-keyed
+    int rc = for_shards(ctx, n, [&](Lane& d, size_t lo, size_t hi) -> int {
+        const size_t cnt = hi - lo;
+        uint8_t s2[32];
+        std::memcpy(s2, seed, 32);
+        for (int k = 0; k < 8; k++) s2[24 + k] ^= (uint8_t)((uint64_t)lo >> (8 * k));
+        thread_local nwv::KeyGrouper kg;  // per-thread scratch, as ed_stage_keyed's
+        const uint8_t* rpk = pk + 32 * lo;
+        int how = 3;
+        if (kg.group(rpk, cnt, keycache_has_all(d, rpk, 1) ? SIZE_MAX : cnt / 2) &&
+            (2 * kg.n_distinct() <= cnt || keycache_has_all(d, kg.distinct(), kg.n_distinct())))
+            how = 2;
+        int r;
+        if (how == 3) {
+            r = ed_stage(d, d.ed, lo, hi, pk, sig, msg_base, msg_off, msg_len, s2);
+        } else {
+            // (the range's own arrays from index 0: key_idx is the range's)
+            r = ed_stage_keyed(d, d.ed, 0, cnt, kg.n_distinct(), kg.distinct(), kg.key_idx(), sig + 64 * lo, msg_base,
+                               msg_off + lo, msg_len + lo, s2, nullptr, true, comb_max);
+            if (!r && d.ed.kc_split) how = 1;
+        }
+        if (r) return r;
+        int ok = 1;
+        r = batch_on_device(d, d.ed, cnt, s2, d.stream, &ok,
+                            verdict_bits_or_null ? verdict_bits_or_null + lo / 64 : nullptr, true);
+        if (r) return r;
+        kc_call_done(d);  // every path of batch_on_device ends with the stream synchronised
+        std::lock_guard<std::mutex> g(omu);
+        if (!ok) *all_valid = 0;
+        how_call = std::max(how_call, how);
+        return NWV_OK;
+    });
+    if (rc == NWV_OK) ctx->n_grouped[how_call]++;
+    return rc;
+}
+
+int nwv_diag_grouped(const nwv_ctx* ctx, uint64_t out[4]) {
+    if (!ctx || !out) return set_err(NWV_ERR_ARG, "null argument");
+    for (int k = 0; k < 4; k++) out[k] = ctx->n_grouped[k].load();
+    return NWV_OK;
+}
+
 // Committee registration (epoch start, Core::change_epoch primary/src/core.rs:592-611): fill the
 // key cache of every device with the committee's keys, so single verifies by them
 // (nwv_ed25519_pubkey_verify, which only looks keys up) take the 128-bit-scalar form.
@@ -2195,12 +2294,15 @@ int nwv_ed25519_pubkey_verify(nwv_ctx* ctx, const uint8_t pk[32], const uint8_t*
 static int shared_msg_batch(nwv_ctx* ctx, size_t n, const uint8_t* pks, const uint8_t* sigs,
                             const uint8_t* msg, size_t msg_len, const uint8_t* seed32) {
     if (msg_len > UINT32_MAX) return set_err(NWV_ERR_ARG, "message too long");
-    std::vector<uint64_t> off(n, 0);
-    std::vector<uint32_t> len(n, (uint32_t)msg_len);
+    // (per-thread scratch: the grouping pass is paid for out of what these allocations cost)
+    thread_local std::vector<uint64_t> off;
+    thread_local std::vector<uint32_t> len;
+    off.assign(n, 0);
+    len.assign(n, (uint32_t)msg_len);
     static const uint8_t empty[1] = {0};
     int all = 0;
-    int rc = nwv_ed25519_verify_batch(ctx, n, pks, sigs, msg_len ? msg : empty, off.data(),
-                                      len.data(), seed32, &all, nullptr);
+    int rc = nwv_ed25519_verify_batch_grouped(ctx, n, pks, sigs, msg_len ? msg : empty, off.data(),
+                                              len.data(), seed32, &all, nullptr);
     if (rc) return rc;
     return all ? NWV_OK : NWV_ERR_SIGNATURE;
 }
@@ -2256,8 +2358,8 @@ int nwv_ed25519_aggregate_batch_verify(nwv_ctx* ctx, size_t n_aggs, const uint8_
         mo += msg_lens[a];
     }
     int all = 0;
-    int rc = nwv_ed25519_verify_batch(ctx, total, P.data(), S.data(), M.data(), off.data(),
-                                      len.data(), seed32, &all, nullptr);
+    int rc = nwv_ed25519_verify_batch_grouped(ctx, total, P.data(), S.data(), M.data(), off.data(),
+                                              len.data(), seed32, &all, nullptr);
     if (rc) return rc;
     return all ? NWV_OK : NWV_ERR_SIGNATURE;
 }

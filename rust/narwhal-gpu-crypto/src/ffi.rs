@@ -231,6 +231,21 @@ extern "C" {
         all_valid: *mut c_int,
         verdict_bits_or_null: *mut u64,
     ) -> c_int;
+    // one key per signature, grouped by key bytes in the library; what the trait-surface calls run on
+    pub fn nwv_ed25519_verify_batch_grouped(
+        ctx: *mut NwvCtx,
+        n: usize,
+        pk: *const u8,
+        sig: *const u8,
+        msg_base: *const u8,
+        msg_off: *const u64,
+        msg_len: *const u32,
+        seed32: *const u8,
+        all_valid: *mut c_int,
+        verdict_bits_or_null: *mut u64,
+    ) -> c_int;
+    // diagnostics: grouped calls, of them cached / keyed uncached / un-keyed; out[4]
+    pub fn nwv_diag_grouped(ctx: *const NwvCtx, out: *mut u64) -> c_int;
     pub fn nwv_ed25519_verify_batch_keyed_digests(
         ctx: *mut NwvCtx,
         n_pre: usize,

@@ -323,6 +323,12 @@ impl Display for GpuEd25519AggregateSignature {
     }
 }
 
+/// `verify` and `batch_verify` hand the library one key per signature; it groups them by their
+/// bytes and looks each distinct key up in the committee key cache.  Once the committee is
+/// registered (`keycache_register`, at start-up and at every epoch change) a certificate's
+/// signatures take the one-launch path (at most 64 signatures) or the comb kernel (larger ones,
+/// and a round's certificates through `batch_verify`); unregistered keys take the batch MSM, keyed
+/// when at most half of them are distinct.  Verdicts never depend on the registration.
 impl AggregateAuthenticator for GpuEd25519AggregateSignature {
     type Sig = GpuEd25519Signature;
     type PubKey = GpuEd25519PublicKey;
@@ -407,6 +413,25 @@ pub fn keycache_retain<K: AsRef<[u8]>>(new_committee: &[K]) -> Result<KeycacheRe
     let rc = unsafe { ffi::nwv_keycache_retain(ctx(), new_committee.len(), p, out.as_mut_ptr()) };
     if rc == ffi::NWV_OK {
         Ok(KeycacheRetained { slots_retired: out[0], combs_retired: out[1], pinned_kept: out[2], used: out[3] })
+    } else {
+        Err(last_error())
+    }
+}
+
+/// Register the committee's Ed25519 keys with every device's key cache (point records and comb
+/// tables): call it once at start-up and in `Core::change_epoch` after `keycache_retain`.  The
+/// trait calls (`verify_batch_empty_fail`, `AggregateAuthenticator::{verify, batch_verify}`) only
+/// look keys up, so this is what sends a committee's certificates down the one-launch and comb
+/// paths.  Registering the same list again is a no-op.
+pub fn keycache_register<K: AsRef<[u8]>>(committee: &[K]) -> Result<(), String> {
+    if committee.iter().any(|k| k.as_ref().len() != PUBLIC_KEY_LENGTH) {
+        return Err("a key is not 32 bytes".into());
+    }
+    let keys = flat(committee.iter());
+    let p = if committee.is_empty() { std::ptr::null() } else { keys.as_ptr() };
+    let rc = unsafe { ffi::nwv_keycache_register(ctx(), committee.len(), p) };
+    if rc == ffi::NWV_OK {
+        Ok(())
     } else {
         Err(last_error())
     }
