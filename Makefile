@@ -41,7 +41,7 @@ oracle:
 
 hostemu: tests/_build/libhostemu.so tests/_build/libsvcstub.so tests/_build/libblsemu.so tests/_build/libblsshard.so \
 	tests/_build/libcombemu.so tests/_build/libfeseeded.so tests/_build/libtrimemu.so tests/_build/libfoldemu.so \
-	tests/_build/libplace.so tests/_build/libkcalloc.so tests/_build/libgroupkeys.so
+	tests/_build/libplace.so tests/_build/libkcalloc.so tests/_build/libgroupkeys.so tests/_build/libeachemu.so
 # the trait surface's grouping of a batch's keys (group_keys.h) with no HIP (tests/test_group_keys_host.py)
 tests/_build/libgroupkeys.so: tests/hostemu/group_keys_stub.cpp narwhal_amd/csrc/group_keys.h
 	@mkdir -p tests/_build
@@ -82,6 +82,10 @@ tests/_build/libhostemu.so: tests/hostemu/hostemu.cpp $(CSRC)
 tests/_build/libcombemu.so: tests/hostemu/comb_hostemu.cpp $(CSRC)
 	@mkdir -p tests/_build
 	$(HIPCC) -std=c++17 -O1 --offload-host-only -x hip -DNWV_BOUNDS_CHECK -fPIC -shared -o $@ tests/hostemu/comb_hostemu.cpp
+# the row kernel's per-signature arithmetic on the host (tests/test_each_row_hostemu.py)
+tests/_build/libeachemu.so: tests/hostemu/each_row_hostemu.cpp $(CSRC)
+	@mkdir -p tests/_build
+	$(HIPCC) -std=c++17 -O1 --offload-host-only -x hip -DNWV_BOUNDS_CHECK -fPIC -shared -o $@ tests/hostemu/each_row_hostemu.cpp
 # fe25519.h's multiply and squaring in every column-sum form, column sums asserted below 2^63
 # (tests/test_fe_seeded_hostemu.py)
 tests/_build/libfeseeded.so: tests/hostemu/fe_seeded_hostemu.cpp narwhal_amd/csrc/fe25519.h

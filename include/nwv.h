@@ -95,6 +95,11 @@ typedef struct nwv_ctx nwv_ctx;
  * that nwv_bls_last_kernel_ms reports only with this flag: the events cost a single verification
  * ~0.1 ms (larger calls always record them) */
 #define NWV_FLAG_BLS_STAGE_TIMES 8192u
+/* diagnostic / tests: a per-signature pass of at most nwv_each_row_max signatures (verify_each, or
+ * the pass that names the bad set after a rejected batch MSM) runs in one launch of the row kernel
+ * (k_ed_each_row); this flag keeps every per-signature pass on the lane pipeline (k_ed_hash,
+ * k_ed_points, k_ed_straus) */
+#define NWV_FLAG_NO_EACH_ROW 16384u
 
 /* ------------------------------------------------------------------ lifecycle ----- */
 /* Process-wide context creation (created once, in Primary::spawn).
@@ -122,6 +127,25 @@ int nwv_diag_counters_ex(const nwv_ctx* ctx, uint64_t* out, int cap);
  * default 16,384) are clamped to just below it.  The getter returns the value in force. */
 int nwv_set_comb_batch_max(nwv_ctx* ctx, size_t n);
 size_t nwv_comb_batch_max(const nwv_ctx* ctx);
+/* Largest per-signature pass that takes the row kernel: a single-device pass of at most n
+ * signatures -- nwv_ed25519_verify_each, or the pass after a rejected batch MSM when verdict bits
+ * were asked for, over any keys, registered or not -- runs in one launch of k_ed_each_row (one
+ * workgroup a signature, the same exact ZIP-215 verdicts) instead of the three launches of the lane
+ * pipeline, unless the context was opened with NWV_FLAG_NO_EACH_ROW or NWV_FLAG_MSM_ALWAYS.
+ * Staged batches (nwv_stage_*) always keep the lane pipeline.  Same semantics as
+ * nwv_set_comb_batch_max: 0 turns the path off, values at or above the shard minimum are clamped
+ * to just below it, the getter returns the value in force. */
+int nwv_set_each_row_max(nwv_ctx* ctx, size_t n);
+size_t nwv_each_row_max(const nwv_ctx* ctx);
+/* Diagnostics, summed over the devices: out[0] per-signature passes run by k_ed_each_row (each of
+ * them also counts as a per-signature pass in nwv_diag_counters out[2]), out[1] the signatures in
+ * those passes. */
+int nwv_diag_each_row(const nwv_ctx* ctx, uint64_t out[2]);
+/* How many of those passes ran the reuse form (k_ed_each_row_msm): after a rejected batch MSM over
+ * per-signature keys the pass loads the MSM's decompressed R and A records, its k_i and its s < l
+ * flags instead of decompressing and hashing again, unless the context was opened with
+ * NWV_FLAG_NO_MSM_REUSE.  verify_each and keyed batches always run the plain form. */
+int nwv_diag_each_row_reuse(const nwv_ctx* ctx, uint64_t* out);
 /* HIP ordinal of the context's i-th device (-1 if out of range) */
 int nwv_device_ordinal(const nwv_ctx* ctx, int i);
 /* Placement: which device object of a multi-device context serves a call.  A call that does not

@@ -37,6 +37,7 @@ NWV_FLAG_NO_EARLY_PREP = 1024
 NWV_FLAG_NO_FUSED_KEYSUM = 2048
 NWV_FLAG_NO_TINY = 4096
 NWV_FLAG_BLS_STAGE_TIMES = 8192  # per-stage timing events on small BLS calls (nwv_bls_last_kernel_ms)
+NWV_FLAG_NO_EACH_ROW = 16384  # every per-signature pass stays on the lane pipeline (no k_ed_each_row)
 NWV_RUN_TIMED = 0x100
 
 
@@ -70,6 +71,10 @@ def load():
         "nwv_diag_device_counters": ([_vp, _i32, _i32, _vp, _i32], _i32),
         "nwv_set_comb_batch_max": ([_vp, _sz], _i32),
         "nwv_comb_batch_max": ([_vp], _sz),
+        "nwv_set_each_row_max": ([_vp, _sz], _i32),
+        "nwv_each_row_max": ([_vp], _sz),
+        "nwv_diag_each_row": ([_vp, _vp], _i32),
+        "nwv_diag_each_row_reuse": ([_vp, _vp], _i32),
         "nwv_abi_version": ([], _i32),
         "nwv_last_error": ([], ctypes.c_char_p),
         "nwv_ed25519_verify_each": ([_vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp], _i32),
@@ -247,6 +252,26 @@ class Engine:
     @property
     def comb_batch_max(self):
         return int(self.lib.nwv_comb_batch_max(self._h))
+
+    def set_each_row_max(self, n):
+        """nwv_set_each_row_max: the largest per-signature pass that takes the row kernel (0: off)"""
+        _check(self.lib.nwv_set_each_row_max(self._h, int(n)))
+
+    @property
+    def each_row_max(self):
+        return int(self.lib.nwv_each_row_max(self._h))
+
+    def diag_each_row(self):
+        """nwv_diag_each_row: (per-signature passes run by k_ed_each_row, signatures in them)"""
+        out = np.zeros(2, dtype=np.uint64)
+        _check(self.lib.nwv_diag_each_row(self._h, out.ctypes.data))
+        return int(out[0]), int(out[1])
+
+    def diag_each_row_reuse(self):
+        """nwv_diag_each_row_reuse: the row kernel's passes that reused a rejected MSM's records"""
+        out = np.zeros(1, dtype=np.uint64)
+        _check(self.lib.nwv_diag_each_row_reuse(self._h, out.ctypes.data))
+        return int(out[0])
 
     def keycache_register(self, keys):
         """nwv_keycache_register: keys, a list of 32-byte keys (the committee, at epoch start)"""

@@ -26,6 +26,7 @@
 #include "msm_kernels.hip"
 #include "tiny_kernels.hip"
 #include "comb_kernels.hip"
+#include "each_kernels.hip"
 #include "group_keys.h"
 #include "keycache_alloc.h"
 #include "place.h"
@@ -261,6 +262,11 @@ struct Gpu {
     // diagnostics (nwv_diag_counters[_ex]): one-launch tiny batches, batch MSMs, per-signature
     // passes, comb batches (k_ed_comb)
     std::atomic<uint64_t> n_tiny{0}, n_msm{0}, n_each{0}, n_comb{0};
+    // per-signature passes of at most each_row_max signatures take k_ed_each_row (the context's
+    // value, nwv_set_each_row_max; 0: off), and how many did (nwv_diag_each_row): passes, signatures
+    std::atomic<size_t> each_row_max{0};
+    // (n_each_row_msm: those of them that reused a rejected MSM's records, nwv_diag_each_row_reuse)
+    std::atomic<uint64_t> n_each_row{0}, n_each_row_sigs{0}, n_each_row_msm{0};
 };
 
 int with_device(Lane& d) {
@@ -472,9 +478,49 @@ int ed_scratch(EdBuffers& b, size_t n) {
 // keys (na = n A points): k_ed_points_msm reuses its decompressions.
 // tables_ready: the batch MSM's early form already built the tables (and k, the flags): only the
 // Straus pass runs, returning at once when the MSM's state words (gate) say it accepted.
+// A pass of at most each_row_max signatures takes the one-launch row kernel instead
+// (each_kernels.hip): k_ed_each_row, or, given msm_pts, k_ed_each_row_msm, which loads the MSM's
+// records, k and flags instead of decompressing and hashing again.  Such a pass is always a whole
+// single-device call, since the limit stays below the shard minimum.  These keep the lane pipeline:
+//   - who == ED_STAGED, a staged batch's pass (its kernel sequence is what the benchmark times);
+//   - the gated form (tables_ready / gate);
+//   - a timed pass (ev: the events bracket the lane pipeline's three kernels; only staged runs ask);
+//   - a context with NWV_FLAG_NO_EACH_ROW or NWV_FLAG_MSM_ALWAYS.
+// (The caller counts the pass in the device's n_each, whichever kernels run it.)
+enum EdCaller { ED_CALL, ED_STAGED };
 int ed_launch(Lane& d, EdBuffers& b, size_t n, hipStream_t stream, hipEvent_t* ev,
-              const uint32_t* msm_pts = nullptr, bool tables_ready = false, const uint32_t* gate = nullptr) {
+              const uint32_t* msm_pts = nullptr, bool tables_ready = false, const uint32_t* gate = nullptr,
+              EdCaller who = ED_CALL) {
     if (n == 0) return NWV_OK;
+    if (who == ED_CALL && !tables_ready && !gate && !ev && d.gpu && n <= d.gpu->each_row_max.load() &&
+        !(d.flags & (NWV_FLAG_NO_EACH_ROW | NWV_FLAG_MSM_ALWAYS))) {
+        const size_t words = (n + 63) / 64;
+        int rc = b.verdict.ensure(8 * words + 8);
+        if (rc) return rc;
+        NWV_HIP(hipMemsetAsync(b.verdict.p, 0, 8 * words, stream));
+        EachArgs a{};
+        a.pk = b.pk.as<uint8_t>();
+        a.sig = b.sig.as<uint8_t>();
+        a.msg = b.msg.as<uint8_t>();
+        a.off = b.off.as<uint64_t>();
+        a.len = b.len.as<uint32_t>();
+        a.bcomb = d.gpu->comb.as<uint32_t>();
+        a.verdict = b.verdict.as<unsigned long long>();
+        if (msm_pts) {  // (msm_reusable: k_msm_prep stored k and the flags with the records)
+            a.pts = msm_pts;
+            a.kbuf = b.kbuf.as<uint32_t>();
+            a.flags = b.flags.as<uint32_t>();
+            a.na = (uint32_t)n;
+            hipLaunchKernelGGL(k_ed_each_row_msm, dim3((unsigned)n), dim3(64 * EACH_WAVES), 0, stream, a);
+            d.gpu->n_each_row_msm++;
+        } else {
+            hipLaunchKernelGGL(k_ed_each_row, dim3((unsigned)n), dim3(64 * EACH_WAVES), 0, stream, a);
+        }
+        NWV_HIP(hipGetLastError());
+        d.gpu->n_each_row++;
+        d.gpu->n_each_row_sigs += n;
+        return NWV_OK;
+    }
     int rc = ed_scratch(b, n);
     if (rc) return rc;
     const size_t waves = (n + 63) / 64;
@@ -1385,6 +1431,13 @@ bool verdicts_all_valid(const uint64_t* bits, size_t n) {
 #ifndef NWV_COMB_BATCH_MAX_DEFAULT
 #define NWV_COMB_BATCH_MAX_DEFAULT 2048
 #endif
+// Largest per-signature pass that takes the row kernel (k_ed_each_row) by default, by the same rule
+// from the sweep of tools/each_row_sweep.py (profiles/each_row_sweep.json), applied to
+// verify_each on valid input and to a rejected verify_batch that asks for the bad set: both
+// qualify at every swept size, up to 4,096.  0: the path is opt-in.
+#ifndef NWV_EACH_ROW_MAX_DEFAULT
+#define NWV_EACH_ROW_MAX_DEFAULT 4096
+#endif
 
 struct nwv_ctx {
     std::vector<Gpu*> devs;
@@ -1396,6 +1449,9 @@ struct nwv_ctx {
     // registered-key batches of TINY_MAX < n <= comb_batch_max signatures take k_ed_comb
     // (nwv_set_comb_batch_max; 0: off; always below shard_min, so only single-range calls)
     std::atomic<size_t> comb_batch_max{NWV_COMB_BATCH_MAX_DEFAULT};
+    // per-signature passes of at most each_row_max signatures take k_ed_each_row
+    // (nwv_set_each_row_max, same clamp; every device object holds a copy for ed_launch)
+    std::atomic<size_t> each_row_max{NWV_EACH_ROW_MAX_DEFAULT};
     // the load of every device object, by which calls are placed (place.h; env NWV_PLACE, read at
     // nwv_init); the BLS12-381 engine shares it when it has as many device objects
     std::shared_ptr<nwv::PlaceTable> place;
@@ -1522,6 +1578,7 @@ static int init_devices(nwv_ctx** out, std::vector<int> ordinals, uint32_t flags
             ctx->devs.push_back(d);
         }
     ctx->place.reset(new nwv::PlaceTable(ctx->devs.size(), nwv::place_mode_from_env()));
+    (void)nwv_set_each_row_max(ctx, NWV_EACH_ROW_MAX_DEFAULT);
     *out = ctx;
     return NWV_OK;
 }
@@ -1596,6 +1653,29 @@ int nwv_set_comb_batch_max(nwv_ctx* ctx, size_t n) {
     return NWV_OK;
 }
 size_t nwv_comb_batch_max(const nwv_ctx* ctx) { return ctx ? ctx->comb_batch_max.load() : 0; }
+int nwv_set_each_row_max(nwv_ctx* ctx, size_t n) {
+    if (!ctx) return set_err(NWV_ERR_ARG, "null context");
+    const size_t v = std::min<size_t>(n, ctx->shard_min - 1);
+    ctx->each_row_max = v;
+    for (Gpu* g : ctx->devs) g->each_row_max = v;
+    return NWV_OK;
+}
+size_t nwv_each_row_max(const nwv_ctx* ctx) { return ctx ? ctx->each_row_max.load() : 0; }
+int nwv_diag_each_row_reuse(const nwv_ctx* ctx, uint64_t* out) {
+    if (!ctx || !out) return set_err(NWV_ERR_ARG, "null argument");
+    *out = 0;
+    for (const Gpu* g : ctx->devs) *out += g->n_each_row_msm.load();
+    return NWV_OK;
+}
+int nwv_diag_each_row(const nwv_ctx* ctx, uint64_t out[2]) {
+    if (!ctx || !out) return set_err(NWV_ERR_ARG, "null argument");
+    out[0] = out[1] = 0;
+    for (const Gpu* g : ctx->devs) {
+        out[0] += g->n_each_row.load();
+        out[1] += g->n_each_row_sigs.load();
+    }
+    return NWV_OK;
+}
 int nwv_device_ordinal(const nwv_ctx* ctx, int i) {
     return (ctx && i >= 0 && i < (int)ctx->devs.size()) ? ctx->devs[i]->ordinal : -1;
 }
@@ -1631,6 +1711,7 @@ int nwv_ed25519_verify_each(nwv_ctx* ctx, size_t n, const uint8_t* pk, const uin
     return for_shards(ctx, n, [&](Lane& d, size_t lo, size_t hi) -> int {
         int rc = ed_stage(d, d.ed, lo, hi, pk, sig, msg_base, msg_off, msg_len, nullptr);
         if (rc) return rc;
+        d.gpu->n_each++;
         if ((rc = ed_launch(d, d.ed, hi - lo, d.stream, nullptr))) return rc;
         const size_t words = (hi - lo + 63) / 64;
         NWV_HIP(hipMemcpyAsync(verdict_bits + lo / 64, d.ed.verdict.p, 8 * words,
@@ -2569,7 +2650,8 @@ int nwv_staged_run(nwv_staged* st, int mode, const uint8_t seed32[32]) {
             }
         }
     } else {
-        rc = ed_launch(st->own, st->buf, st->n, st->stream, timed ? st->ev : nullptr);
+        rc = ed_launch(st->own, st->buf, st->n, st->stream, timed ? st->ev : nullptr, /*msm_pts*/ nullptr,
+                       /*tables_ready*/ false, /*gate*/ nullptr, ED_STAGED);
     }
     if (rc) return rc;
     st->last_mode = mode;
@@ -2616,7 +2698,8 @@ int nwv_staged_fetch(nwv_staged* st, uint64_t* verdict_bits, int* all_valid) {
             if (all_valid) *all_valid = 1;
             return NWV_OK;
         }
-        if ((rc = ed_launch(st->own, st->buf, st->n, st->stream, nullptr, msm_reusable(st->own, st->buf, true))))
+        if ((rc = ed_launch(st->own, st->buf, st->n, st->stream, nullptr, msm_reusable(st->own, st->buf, true),
+                            /*tables_ready*/ false, /*gate*/ nullptr, ED_STAGED)))
             return rc;
     }
     if (words && !st->buf.verdict.p) return set_err(NWV_ERR_ARG, "staged batch has not run");

@@ -48,6 +48,7 @@ pub const NWV_FLAG_BLS_BATCH: u32 = 128;
 pub const NWV_FLAG_NO_SIGCACHE: u32 = 256;
 /// Keyed batches of <= 64 signatures by registered keys go through the batch MSM, not k_ed_tiny.
 pub const NWV_FLAG_NO_TINY: u32 = 4096;
+pub const NWV_FLAG_NO_EACH_ROW: u32 = 16384;
 /// BLS12-381 calls of <= 1,024 items record the per-stage timing events (nwv_bls_last_kernel_ms).
 pub const NWV_FLAG_BLS_STAGE_TIMES: u32 = 8192;
 
@@ -184,6 +185,10 @@ extern "C" {
     pub fn nwv_diag_counters_ex(ctx: *const NwvCtx, out: *mut u64, cap: c_int) -> c_int;
     pub fn nwv_set_comb_batch_max(ctx: *mut NwvCtx, n: usize) -> c_int;
     pub fn nwv_comb_batch_max(ctx: *const NwvCtx) -> usize;
+    pub fn nwv_set_each_row_max(ctx: *mut NwvCtx, n: usize) -> c_int;
+    pub fn nwv_each_row_max(ctx: *const NwvCtx) -> usize;
+    pub fn nwv_diag_each_row(ctx: *const NwvCtx, out: *mut u64) -> c_int;
+    pub fn nwv_diag_each_row_reuse(ctx: *const NwvCtx, out: *mut u64) -> c_int;
     pub fn nwv_device_ordinal(ctx: *const NwvCtx, i: c_int) -> c_int;
     pub fn nwv_diag_device_counters(
         ctx: *mut NwvCtx,
