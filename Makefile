@@ -41,7 +41,8 @@ oracle:
 
 hostemu: tests/_build/libhostemu.so tests/_build/libsvcstub.so tests/_build/libblsemu.so tests/_build/libblsshard.so \
 	tests/_build/libcombemu.so tests/_build/libfeseeded.so tests/_build/libtrimemu.so tests/_build/libfoldemu.so \
-	tests/_build/libplace.so tests/_build/libkcalloc.so tests/_build/libgroupkeys.so tests/_build/libeachemu.so
+	tests/_build/libplace.so tests/_build/libkcalloc.so tests/_build/libgroupkeys.so tests/_build/libeachemu.so \
+	tests/_build/libblswbemu.so
 # the trait surface's grouping of a batch's keys (group_keys.h) with no HIP (tests/test_group_keys_host.py)
 tests/_build/libgroupkeys.so: tests/hostemu/group_keys_stub.cpp narwhal_amd/csrc/group_keys.h
 	@mkdir -p tests/_build
@@ -63,6 +64,11 @@ tests/_build/libblsshard.so: tests/hostemu/bls_shard_stub.cpp narwhal_amd/csrc/b
 tests/_build/libblsemu.so: tests/hostemu/bls_hostemu.cpp $(BLS_SRC) $(BLS_SHARED)
 	@mkdir -p tests/_build
 	$(HIPCC) -std=c++17 -O2 --offload-host-only -x hip -fPIC -shared -o $@ tests/hostemu/bls_hostemu.cpp
+# the wave engine's batch check (one final exponentiation a group) on the host
+# (tests/test_bls_wave_batch_hostemu.py)
+tests/_build/libblswbemu.so: tests/hostemu/bls_wave_batch_hostemu.cpp $(BLS_SRC) $(BLS_SHARED)
+	@mkdir -p tests/_build
+	$(HIPCC) -std=c++17 -O2 --offload-host-only -x hip -fPIC -shared -o $@ tests/hostemu/bls_wave_batch_hostemu.cpp
 # the same build under AddressSanitizer + UndefinedBehaviorSanitizer (host code only):
 #   make blsemu-asan && tools/run_blsemu_asan.sh
 tests/_build/libblsemu_asan.so: tests/hostemu/bls_hostemu.cpp $(BLS_SRC) $(BLS_SHARED)

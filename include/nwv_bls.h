@@ -61,13 +61,34 @@ int nwv_bls_verify_many(nwv_ctx* ctx, size_t n_keys, const uint8_t* keys, size_t
 /* device time of the last nwv_bls_verify_many call on this context, per stage (HIP events; the
  * first four run on three concurrent streams): [0] keys new to the device's key cache, [1]
  * signature decode + G1 checks, [2] hash to G1, [3] key sums, [4] the pairing check (the batch
- * check k_bls_rlc + k_bls_fold + k_bls_final, plus k_bls_pair when it ran).  Calls of at most
+ * check k_bls_rlc + k_bls_fold + k_bls_final, plus k_bls_pair when it ran; the whole wave batch
+ * check, any per-item re-check included).  Calls of at most
  * 1,024 items record these only on a context opened with NWV_FLAG_BLS_STAGE_TIMES (else zeros). */
 int nwv_bls_last_kernel_ms(nwv_ctx* ctx, double out_ms[5]);
 /* how the last nwv_bls_verify_many call checked its pairings: 0 per item on the 8-lane group
  * kernels (NWV_FLAG_BLS_PER_ITEM), 1 one batch check that accepted every item and 2 a batch check
  * that rejected, then per item (NWV_FLAG_BLS_BATCH), 3 every item on its own wave (the default) */
 int nwv_bls_last_path(nwv_ctx* ctx);
+/* two more codes of nwv_bls_last_path, from the wave batch check below: 4 it ran and every group
+ * accepted, 5 some group rejected and that group's items were then checked per item */
+
+/* The wave batch check: a large wave call (more than NWV_BLS_WAVE_MAX = 1,024 items, neither
+ * NWV_FLAG_BLS_PER_ITEM nor NWV_FLAG_BLS_BATCH) of at least n items -- or a device's share of one,
+ * when the context splits the call -- is checked group by group: the items whose decode, G1 and
+ * key statuses are OK are split into consecutive groups (env NWV_BLS_BATCH_GROUP items, default
+ * 16), every item runs its Miller loop alone, and a group runs ONE final exponentiation over the
+ * product of its items' Miller outputs weighted by per-call random 64-bit coefficients.  The items
+ * of a group that rejects (and of accepted groups between rejected ones less than 1,024 items
+ * apart) run the per-item check, so statuses stay exact.  n = 0 (the
+ * default) turns it off: every call then takes exactly the path it takes without this setting.
+ * Calls of at most NWV_BLS_WAVE_MAX items never take it whatever n is: they are bound by the
+ * latency of one item's chain on one wave, which a shared final exponentiation does not shorten.
+ * Every entry point that verifies through nwv_bls_verify_many inherits the setting. */
+int nwv_bls_set_wave_batch_min(nwv_ctx* ctx, size_t n);
+size_t nwv_bls_wave_batch_min(const nwv_ctx* ctx);
+/* the wave batch check of the last nwv_bls_verify_many call: out[0] groups formed, out[1] groups
+ * that rejected, out[2] items re-checked per item (zeros when the check did not run) */
+int nwv_bls_last_batch(nwv_ctx* ctx, uint64_t out[3]);
 /* keys of the last nwv_bls_verify_many call: out[0] key-list entries found in the key cache,
  * out[1] distinct keys the call decoded itself */
 int nwv_bls_last_keys(nwv_ctx* ctx, uint64_t out[2]);

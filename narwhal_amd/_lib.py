@@ -106,6 +106,9 @@ def load():
         "nwv_staged_mark": ([_vp, _i32], _i32),
         "nwv_staged_mark_elapsed": ([_vp, _i32, _vp, _i32, ctypes.POINTER(ctypes.c_float)], _i32),
         "nwv_ed25519_sign_many": ([_vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp], _i32),
+        "nwv_bls_set_wave_batch_min": ([_vp, _sz], _i32),
+        "nwv_bls_wave_batch_min": ([_vp], _sz),
+        "nwv_bls_last_batch": ([_vp, _vp], _i32),
     }
     for name, (args, res) in sig.items():
         f = getattr(lib, name)

@@ -33,7 +33,8 @@ _SIGS = {
     "nwv_bls_keycache_size": ([_vp], _i32),
 }
 KERNELS = ("keys_new_to_cache", "sig_decode", "hash_to_g1", "key_sums", "pairing_check")
-PATHS = ("per_item", "batch_accepted", "batch_rejected_then_per_item", "wave")
+PATHS = ("per_item", "batch_accepted", "batch_rejected_then_per_item", "wave", "wave_batch_accepted",
+         "wave_batch_rejected_then_per_item")
 _bound = set()
 
 
@@ -113,7 +114,20 @@ class Bls:
 
     def last_path(self):
         """how the last verify_many checked its pairings (PATHS)"""
-        return PATHS[_lib._check(self.lib.nwv_bls_last_path(self._h), allow=(0, 1, 2, 3))]
+        return PATHS[_lib._check(self.lib.nwv_bls_last_path(self._h), allow=range(len(PATHS)))]
+
+    # the wave batch check of large calls (one final exponentiation per group): off at 0
+    def set_wave_batch_min(self, n):
+        _lib._check(self.lib.nwv_bls_set_wave_batch_min(self._h, n))
+
+    def wave_batch_min(self):
+        return int(self.lib.nwv_bls_wave_batch_min(self._h))
+
+    def last_batch(self):
+        """(groups formed, groups rejected, items re-checked per item) of the last verify_many"""
+        out = np.zeros(3, dtype=np.uint64)
+        _lib._check(self.lib.nwv_bls_last_batch(self._h, out.ctypes.data))
+        return int(out[0]), int(out[1]), int(out[2])
 
     # the committee key cache: register at epoch start, reset at an epoch change
     def register_keys(self, keys):

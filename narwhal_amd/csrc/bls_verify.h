@@ -382,6 +382,128 @@ NWV_HD bool w_pairing_check_h(const W& w, const uint32_t* sig_rec, const uint32_
     return w_pairing_check_g(w, sig_rec, hh_rec, true, apk_rec, false, qlines);
 }
 
+// ---- the batch check on the wave engine: one final exponentiation per GROUP of items ----------
+// A large call's OK-status items are split into consecutive groups; group g accepts iff
+//   (prod_{i in g} f([r_i] H_i, apk_i)) f(-S_g, g2), S_g = sum_{i in g} [r_i] sig_i,
+// raised to the final exponent is 1 (f = the Miller loop alone, wave::miller_script; r_i =
+// rlc_scalar).  Stages: wb_points per item (a lane for each of the two); a per-group tree of rlc_sfold;
+// wb_sig_item per group; the Miller loops of the n items and of one signature item per group on
+// the packed wave kernel; w_ffold_step trees over the F records; w_group_final on each group's
+// last wave.  An item outside the batch (a failed status, an identity signature) enters with
+// neutral points and its F record is written as 1.
+//
+// An F record: the 12 F slots as the wave holds them, then the number of Miller outputs folded
+// into it (1 from a Miller wave whose script ran, 0 otherwise), then a pad word.  A group's last
+// wave accepts only when that count is the group's items + 1, so a Miller launch that found no
+// script or a tree level that did not run rejects the group.
+constexpr int FB_REC_WORDS = 12 * NL + 2;
+constexpr int G2J_REC_WORDS = 6 * NL + 1;  // a Jacobian G2 record: X, Y, Z (Fp2 each), identity flag
+constexpr uint32_t WB_FAN = 17;  // records one wave multiplies at a tree level (16 items + their signature item)
+
+// item i's points: p_out = [r] H as a homogeneous record (X Z, Y, Z^3 of the Jacobian multiple: the
+// form pair_flat takes with h_hom, no inversion), s_out = [r] sig (Jacobian record).  The two
+// multiplications are independent: the kernel gives each a lane of its own.
+NWV_HD void wb_point_h(const uint32_t* h_rec, uint64_t r, uint32_t* p_out) {
+    jac<fp> h;
+    h.inf = true;
+    h.x = h.y = h.z = fp_zero();
+    if (!h_rec[2 * NL]) h = jac_mul64(jac_from_affine(ld_fp(h_rec), ld_fp(h_rec + NL)), r);
+    if (h.inf) {
+        st_g1j(p_out, h);
+        return;
+    }
+    st_fp(p_out, fp_mul(h.x, h.z));
+    st_fp(p_out + NL, h.y);
+    st_fp(p_out + 2 * NL, fp_mul(fp_sqr(h.z), h.z));
+    p_out[3 * NL] = 0u;
+}
+NWV_HD void wb_point_s(const uint32_t* sig_rec, uint64_t r, uint32_t* s_out) {
+    jac<fp> s;
+    s.inf = true;
+    s.x = s.y = s.z = fp_zero();
+    if (!sig_rec[2 * NL]) s = jac_mul64(jac_from_affine(ld_fp(sig_rec), ld_fp(sig_rec + NL)), r);
+    st_g1j(s_out, s);
+}
+NWV_HD void wb_points(const uint32_t* sig_rec, const uint32_t* h_rec, uint64_t r, uint32_t* p_out, uint32_t* s_out) {
+    wb_point_h(h_rec, r, p_out);
+    wb_point_s(sig_rec, r, s_out);
+}
+// an item outside the batch: identity on both sides (g_rlc_neutral's records; G1J_REC_WORDS =
+// G1H_REC_WORDS, the flag in the last word)
+NWV_HD void wb_neutral_rec(uint32_t* out) {
+    jac<fp> s;
+    s.inf = true;
+    s.x = s.y = s.z = fp_zero();
+    st_g1j(out, s);
+}
+NWV_HD void wb_neutral(uint32_t* p_out, uint32_t* s_out) {
+    wb_neutral_rec(s_out);
+    wb_neutral_rec(p_out);
+}
+static_assert(G1J_REC_WORDS == 3 * NL + 1, "a neutral Jacobian record is a neutral homogeneous one");
+// an identity signature's item stays out of the batch: its equation is e(H, apk) == 1 with apk of
+// order r, which holds only when H's G1 component is the identity -- H itself, or [h_eff] H0 for
+// a key-side item (kmode: h_rec holds H0)
+NWV_HD bool wb_identity_sig_holds(const uint32_t* h_rec, bool kmode) {
+    if (h_rec[2 * NL]) return true;
+    if (!kmode) return false;
+    return jac_mul64(jac_from_affine(ld_fp(h_rec), ld_fp(h_rec + NL)), BLS_H_EFF).inf;
+}
+// group g's signature item: S_g (the group's first Jacobian record after the tree) as an affine
+// signature record (the Miller kernel pairs -S_g with g2 as it pairs -sig), identity on its hash
+// side, g2 as the Q of its unused pair
+NWV_HD void wb_sig_item(const uint32_t* s_rec, uint32_t* sg_out, uint32_t* p_out, uint32_t* q_out) {
+    const jac<fp> S = ld_g1j(s_rec);
+    fp x = fp_zero(), y = fp_zero();
+    if (!S.inf) g1_to_affine(x, y, S);
+    st_g1(sg_out, x, y, S.inf);
+    jac<fp> o;
+    o.inf = true;
+    o.x = o.y = o.z = fp_zero();
+    st_g1j(p_out, o);
+    const fp2 gx = k_g2x(), gy = k_g2y();
+    st_fp(q_out, gx.c0);
+    st_fp(q_out + NL, gx.c1);
+    st_fp(q_out + 2 * NL, gy.c0);
+    st_fp(q_out + 3 * NL, gy.c1);
+    st_fp(q_out + 4 * NL, k_one());
+    st_fp(q_out + 5 * NL, fp_zero());
+    q_out[6 * NL] = 0u;
+}
+// level h of a group's signature tree over its live entries [0, min(m, gsize)): entry j takes entry
+// j + h, h = ceil(m / 2) (k_bls_sfold's shape, per group)
+NWV_HD void wb_sfold(uint32_t* grp, uint32_t j, uint32_t m, uint32_t gsize) {
+    const uint32_t h = (m + 1) / 2, live = m < gsize ? m : gsize;
+    if (j < h && j + h < live) rlc_sfold(grp + (size_t)G1J_REC_WORDS * j, grp + (size_t)G1J_REC_WORDS * (j + h));
+}
+// one step of a group's product tree on a wave (a bank of NSLOTS_PC slots): F <- the product of
+// the records at positions p0, p0 + s, ... below m, at most fan of them (the kernels: WB_FAN);
+// at(p) = position p's record.  Returns the Miller outputs the product holds.
+template <class W, class At>
+NWV_HD uint32_t w_ffold_step(const W& w, At at, uint32_t p0, uint32_t s, uint32_t m, uint32_t fan) {
+    using namespace wave;
+    init_slots_pc(w);
+    const uint32_t* r0 = at(p0);
+    w.put_words(REG_F, r0, 12);
+    uint32_t cnt = r0[12 * NL];
+    w.sync();
+    for (uint32_t q = 1; q < fan && p0 + q * s < m; q++) {
+        const uint32_t* r = at(p0 + q * s);
+        w.put_words(REG_B, r, 12);
+        w.sync();
+        w.run(P_MUL_F_B);
+        cnt += r[12 * NL];
+    }
+    return cnt;
+}
+// a group's verdict from its whole product in F: conjugation, final exponentiation, == 1
+template <class W>
+NWV_HD bool w_group_final(const W& w) {
+    using namespace wave;
+    w.run(P_CONJ_F);
+    final_exp(w);
+    return w.f_is_one();
+}
 
 // ---- AggregateAuthenticator::aggregate (types/src/primary.rs:476-477) on a wave: g1_sum16 adds
 // G1SUM_N points with complete formulas (the identity and equal points need no branches); point k

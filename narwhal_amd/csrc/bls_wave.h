@@ -793,8 +793,9 @@ NWV_HD bool pairing_check(const W& w, const uint32_t* qlines, bool two_step = tr
 }
 
 // the ops of pairing_check after its set-up (F = 1, TB = QB): the Miller loop with precomputed key
-// lines (fixed) or computed ones, the conjugation, the final exponentiation.  Returns the count.
-inline int pairing_script(bool fixed, SOp* ops) {
+// lines (fixed) or computed ones, then (with_final) the conjugation and the final exponentiation.
+// Returns the count.
+inline int script_ops(bool fixed, bool with_final, SOp* ops) {
     int n = 0;
     const ScriptRec w{ops, &n};
     const char* steps = BLS_WAVE_STEPS_STR;
@@ -806,8 +807,10 @@ inline int pairing_script(bool fixed, SOp* ops) {
         ops[n++] = SOp{(uint32_t)k, 0u, 1u | (SOP_LINES << 16), -1};
         w.run(steps[k] == 'a' ? pa : pd);
     }
-    w.run(P_CONJ_F);
-    final_exp(w);
+    if (with_final) {
+        w.run(P_CONJ_F);
+        final_exp(w);
+    }
     int nxt = -1;
     for (int i = n - 1; i >= 0; i--) {
         ops[i].next_run = nxt;
@@ -815,6 +818,10 @@ inline int pairing_script(bool fixed, SOp* ops) {
     }
     return n;
 }
+inline int pairing_script(bool fixed, SOp* ops) { return script_ops(fixed, true, ops); }
+// the Miller loop alone: pairing_script cut before P_CONJ_F (the wave batch check runs one final
+// exponentiation over a group's product of these, bls_verify.h)
+inline int miller_script(bool fixed, SOp* ops) { return script_ops(fixed, false, ops); }
 
 }  // namespace wave
 }  // namespace bls

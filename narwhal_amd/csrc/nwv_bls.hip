@@ -20,6 +20,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cstdlib>
 #include <cstring>
 #include <functional>
@@ -435,8 +436,15 @@ __device__ __forceinline__ void blsw_pair_item(uint32_t* wm, uint32_t i, const u
 // wrote ~616 KB of scratch per item).  The banks share one P << k table at the front of the LDS
 // (9.6 KB a bank instead of 10.5 KB).
 constexpr int BLS_PACK_MAX = 4;
+// items per group of the wave batch check (env NWV_BLS_BATCH_GROUP overrides)
+#ifndef NWV_BLS_BATCH_GROUP_DEFAULT
+#define NWV_BLS_BATCH_GROUP_DEFAULT 16
+#endif
 __device__ wave::SOp g_pair_script[2][wave::SCRIPT_MAX];  // [fixed key lines]
 __device__ int g_pair_script_n[2];
+// the Miller loop alone (wave::miller_script): the wave batch check's per-item pass
+__device__ wave::SOp g_mill_script[2][wave::SCRIPT_MAX];
+__device__ int g_mill_script_n[2];
 // two waves per SIMD (<= 256 registers: at most 4 terms' LDS reads in flight, NWV_BLS_PAIR_TERMS)
 // with three items a wave (NWV_BLS_PACK: 3 x 6.5 KB banks -- registers never live together share
 // slots, tools/gen_bls_wave.py PC_ALIAS -- + the shared 0.9 KB table = 8 waves per CU): 16,384
@@ -456,13 +464,24 @@ __device__ __forceinline__ int lane_div(int x, int d) {
     return (int)(((uint32_t)x * m) >> 16);
 }
 __device__ __forceinline__ int lane_mod(int x, int d) { return x - lane_div(x, d) * d; }
+// the Miller-only form's extra arguments (MILLER): entries [0, n_items) of the grid are the call's
+// items, each with the identity on its signature side (srec, st_dec, st_apk and st_pair are not
+// read); entry n_items + g is group g's signature item: sgrec's record g against g2's own line
+// table, the identity on its hash side.  Every entry's F goes to frec (FB_REC_WORDS each) in
+// place of a verdict; an item with inb = 0 (outside the batch) writes 1.
+struct MillArgs {
+    uint32_t n_items;
+    const uint32_t* sgrec;
+    const uint32_t* inb;
+    uint32_t* frec;
+};
 // items [i0, i0 + k) on this wave: lds_k = the P << k table, then k banks; G: term reads in flight
-template <int G>
+template <int G, bool MILLER = false>
 __device__ __forceinline__ void pair_flat(uint32_t* lds_k, uint32_t i0, int k, const uint32_t* srec,
                                           const int32_t* st_dec, const uint32_t* hrec, int h_hom,
                                           const uint32_t* arec, const int32_t* st_apk, const KeyTab& kt,
                                           const uint32_t* pk_off, const uint32_t* pk_cnt, const uint32_t* pk_idx,
-                                          const uint32_t* kmode, int32_t* st_pair) {
+                                          const uint32_t* kmode, int32_t* st_pair, const MillArgs* ma = nullptr) {
     using namespace wave;
     const int lane = (int)threadIdx.x;
     constexpr uint32_t bankw = (uint32_t)(SW * NSLOTS_PC);
@@ -474,7 +493,13 @@ __device__ __forceinline__ void pair_flat(uint32_t* lds_k, uint32_t i0, int k, c
     bool fixed = true;
     for (int j = 0; j < k; j++) {
         const uint32_t i = i0 + j;
-        sig[j] = srec + (size_t)G1_REC_WORDS * i;
+        if (MILLER && i >= ma->n_items) {  // a group's signature item
+            sig[j] = ma->sgrec + (size_t)G1_REC_WORDS * (i - ma->n_items);
+            hr[j] = hrec + (size_t)G1H_REC_WORDS * i;
+            ql[j] = &T_G2_LINES[0][0][0];
+            continue;
+        }
+        sig[j] = MILLER ? nullptr : srec + (size_t)G1_REC_WORDS * i;
         hr[j] = hrec + (size_t)(h_hom ? G1H_REC_WORDS : G1_REC_WORDS) * i;
         ql[j] = (kt.lines && kmode && kmode[i] && pk_cnt[i] == 1) ? kt.lines + KL_WORDS * pk_idx[pk_off[i]] : nullptr;
         fixed = fixed && ql[j] != nullptr;
@@ -491,7 +516,7 @@ __device__ __forceinline__ void pair_flat(uint32_t* lds_k, uint32_t i0, int k, c
     w.sync();
     for (int j = 0; j < k; j++) {
         const uint32_t i = i0 + j;
-        if (!sig[j][2 * NL]) {
+        if ((!MILLER || sig[j]) && !sig[j][2 * NL]) {
             w.put_words(j, REG_PA, sig[j], 1);
             w.put_fp(j, REG_PA + 1, fp_neg(ld_fp(sig[j] + NL)));
         }
@@ -525,8 +550,8 @@ __device__ __forceinline__ void pair_flat(uint32_t* lds_k, uint32_t i0, int k, c
         }
     };
     fetch(0);
-    const SOp* script = g_pair_script[fixed ? 1 : 0];
-    const int nops = g_pair_script_n[fixed ? 1 : 0];
+    const SOp* script = MILLER ? g_mill_script[fixed ? 1 : 0] : g_pair_script[fixed ? 1 : 0];
+    const int nops = MILLER ? g_mill_script_n[fixed ? 1 : 0] : g_pair_script_n[fixed ? 1 : 0];
     auto first_rec = [&](const SOp& o) { return load_rec(T_DATA + o.a + (uint32_t)lane_mod(lane, (int)(o.b >> 16)) * REC); };
     Rec cur = first_rec(script[0].c >> 16 == SOP_RUN ? script[0] : script[script[0].next_run]);
     int step = 0;
@@ -591,6 +616,24 @@ __device__ __forceinline__ void pair_flat(uint32_t* lds_k, uint32_t i0, int k, c
             s = wrap ? 0 : s + 1;
         }
     }
+    if (MILLER) {
+        // fail closed: a pass that found no script (or not all of its steps) writes F = 0 and
+        // counts no Miller output, so its group's last wave rejects
+        const bool ran = nops > 0 && step == NSTEPS;
+        const fp one = k_one();
+        for (int j = 0; j < k; j++) {
+            const uint32_t i = i0 + j;
+            const bool live = i >= ma->n_items || ma->inb[i] != 0;
+            uint32_t* o = ma->frec + (size_t)FB_REC_WORDS * i;
+            for (int t = lane; t < 12 * SW; t += 64)
+                o[t] = !ran ? 0u : live ? w.bk(j)[SW * REG_F + t] : t < NL ? one.l[t] : 0u;
+            if (lane == 0) {
+                o[12 * SW] = ran ? 1u : 0u;
+                o[12 * SW + 1] = 0u;
+            }
+        }
+        return;
+    }
     const uint32_t ok = w.f_is_one_mask();
     if (lane == 0)
         for (int j = 0; j < k; j++) {
@@ -608,6 +651,101 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NWV_BLS_PAIR
     pair_flat<NWV_BLS_PAIR_TERMS>(lds_k, i0, (int)(n - i0 < kper ? n - i0 : kper), srec, st_dec, hrec, h_hom, arec,
                                   st_apk, kt, pk_off, pk_cnt, pk_idx, kmode, st_pair);
 }
+// The wave batch check (bls_verify.h): one final exponentiation per group of `grp` consecutive
+// items instead of one per item.
+//   k_blsw_rlc_pts   two lanes per item: [r_i] H_i (homogeneous) and [r_i] sig_i (Jacobian); an item
+//                    outside the batch (a failed status, an identity signature) writes neutral
+//                    records, inb = 0 and its own pairing verdict
+//   k_blsw_sfold     the levels of every group's G1 tree: S_g = sum [r_i] sig_i
+//   k_blsw_sig_items one lane per group: S_g affine, entry n + g of the Miller grid
+//   k_blsw_mill_k    the Miller loops of the n items and the groups' signature items, packed as
+//                    k_blsw_pair_k packs (pair_flat over wave::miller_script), F records out
+//   k_blsw_ffold     the levels of every group's product tree, WB_FAN records a wave; the last
+//                    level's wave (one per group) runs the final exponentiation, verdict word out
+//   k_blsw_mark      st_pair of the items inside the batch from their group's verdict
+__global__ __launch_bounds__(BLS_LANES) void k_blsw_rlc_pts(uint32_t n, const uint32_t* srec, const uint32_t* hrec,
+                                                            const int32_t* st_dec, const int32_t* st_apk,
+                                                            const uint32_t* kmode, const uint8_t* seed, uint32_t* prec,
+                                                            uint32_t* jrec, uint32_t* inb, int32_t* st_pair) {
+    // two lanes an item: the even one takes [r] H (and the item's flags), the odd one [r] sig; both
+    // walk the same scalar, so a pair never diverges
+    const uint32_t t = blockIdx.x * BLS_LANES + threadIdx.x, i = t >> 1;
+    if (i >= n) return;
+    const bool sig_side = (t & 1u) != 0;
+    uint32_t* p = prec + (size_t)G1H_REC_WORDS * i;
+    uint32_t* s = jrec + (size_t)G1J_REC_WORDS * i;
+    const uint32_t* sr = srec + (size_t)G1_REC_WORDS * i;
+    const uint32_t* hr = hrec + (size_t)G1_REC_WORDS * i;
+    const bool ok = st_dec[i] == ST_OK && st_apk[i] == ST_OK;
+    if (!ok || sr[2 * NL]) {
+        wb_neutral_rec(sig_side ? s : p);
+        if (sig_side) return;
+        inb[i] = 0u;
+        st_pair[i] = ok && wb_identity_sig_holds(hr, kmode && kmode[i]) ? ST_OK : ST_VERIFY_FAIL;
+        return;
+    }
+    const uint64_t r = rlc_scalar(seed, i);
+    if (sig_side) {
+        wb_point_s(sr, r, s);
+    } else {
+        wb_point_h(hr, r, p);
+        inb[i] = 1u;
+    }
+}
+// level m of the groups' G1 trees: lane (g, j), j < ceil(m / 2)
+__global__ __launch_bounds__(BLS_LANES) void k_blsw_sfold(uint32_t n_items, uint32_t grp, uint32_t ng, uint32_t m,
+                                                          uint32_t* jrec) {
+    const uint32_t h = (m + 1) / 2, n = ng * h;
+    BLS_IDX();
+    const uint32_t g = i / h, j = i % h, lo = g * grp;
+    wb_sfold(jrec + (size_t)G1J_REC_WORDS * lo, j, m, min(grp, n_items - lo));
+}
+__global__ __launch_bounds__(BLS_LANES) void k_blsw_sig_items(uint32_t n_items, uint32_t grp, uint32_t n,
+                                                              const uint32_t* jrec, uint32_t* sgrec, uint32_t* prec,
+                                                              uint32_t* arec) {
+    BLS_IDX();
+    wb_sig_item(jrec + (size_t)G1J_REC_WORDS * i * grp, sgrec + (size_t)G1_REC_WORDS * i,
+                prec + (size_t)G1H_REC_WORDS * (n_items + i), arec + (size_t)G2J_WORDS * (n_items + i));
+}
+static_assert(G2J_WORDS == G2J_REC_WORDS, "wb_sig_item writes the key sums' record form");
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NWV_BLS_PAIR_WAVES))) void k_blsw_mill_k(
+    uint32_t n, uint32_t kper, MillArgs ma, const uint32_t* prec, const uint32_t* arec, KeyTab kt,
+    const uint32_t* pk_off, const uint32_t* pk_cnt, const uint32_t* pk_idx, const uint32_t* kmode) {
+    extern __shared__ uint32_t lds_k[];
+    const uint32_t i0 = blockIdx.x * kper;
+    if (i0 >= n) return;
+    pair_flat<NWV_BLS_PAIR_TERMS, true>(lds_k, i0, (int)(n - i0 < kper ? n - i0 : kper), nullptr, nullptr, prec, 1, arec,
+                                        nullptr, kt, pk_off, pk_cnt, pk_idx, kmode, nullptr, &ma);
+}
+// stride s of the groups' product trees: wave wv of group g multiplies the group's records at
+// positions (wv WB_FAN + q) s, q < WB_FAN, below the group's items + 1 (position p < items: item
+// g grp + p; position items: the group's signature item n_items + g) into the first of them.  With
+// one wave a group (last) the product is the group's whole: that wave accepts when it holds every
+// Miller output of the group and its final exponentiation is 1.  gok[g] was zeroed before the tree.
+__global__ __launch_bounds__(64) void k_blsw_ffold(uint32_t n_items, uint32_t grp, uint32_t wpg, uint32_t s, int last,
+                                                   uint32_t* frec, int32_t* gok) {
+    BLSW_LDS(wave::NSLOTS_PC);
+    const uint32_t g = blockIdx.x / wpg, wv = blockIdx.x % wpg, lo = g * grp;
+    if (lo >= n_items) return;
+    const uint32_t gsize = min(grp, n_items - lo), m = gsize + 1, p0 = wv * WB_FAN * s;
+    if (p0 >= m) return;
+    const wave::Wave w{wm, (int)threadIdx.x};
+    auto at = [&](uint32_t p) { return frec + (size_t)FB_REC_WORDS * (p < gsize ? lo + p : n_items + g); };
+    const uint32_t cnt = w_ffold_step(w, at, p0, s, m, WB_FAN);
+    if (last) {
+        const bool ok = w_group_final(w);
+        if (threadIdx.x == 0) gok[g] = (ok && cnt == m) ? 1 : 0;
+        return;
+    }
+    uint32_t* o = at(p0);
+    w.get_words(wave::REG_F, o, 12);
+    if (threadIdx.x == 0) o[12 * NL] = cnt;
+}
+__global__ __launch_bounds__(BLS_LANES) void k_blsw_mark(uint32_t n, uint32_t grp, const int32_t* gok,
+                                                         const uint32_t* inb, int32_t* st_pair) {
+    BLS_IDX();
+    if (inb[i]) st_pair[i] = gok[i / grp] == 1 ? ST_OK : ST_VERIFY_FAIL;
+}
 // the flat scripts into g_pair_script on the calling thread's device, once per device
 static int ensure_pair_script() {
     static std::mutex mu;
@@ -623,6 +761,10 @@ static int ensure_pair_script() {
     if (hipMemcpyToSymbol(HIP_SYMBOL(g_pair_script), ops, sizeof(ops)) != hipSuccess ||
         hipMemcpyToSymbol(HIP_SYMBOL(g_pair_script_n), cnt, sizeof(cnt)) != hipSuccess)
         return nwv_internal_set_err(NWV_ERR_HIP, "pair script copy");
+    for (int f = 0; f < 2; f++) cnt[f] = wave::miller_script(f != 0, ops[f]);
+    if (hipMemcpyToSymbol(HIP_SYMBOL(g_mill_script), ops, sizeof(ops)) != hipSuccess ||
+        hipMemcpyToSymbol(HIP_SYMBOL(g_mill_script_n), cnt, sizeof(cnt)) != hipSuccess)
+        return nwv_internal_set_err(NWV_ERR_HIP, "miller script copy");
     done[dev] = true;
     return NWV_OK;
 }
@@ -1062,6 +1204,10 @@ struct BlsDev {
     double last_ms[5] = {0, 0, 0, 0, 0};
     int last_path = 0;
     uint64_t last_keys[2] = {0, 0};  // key-list entries found in the cache, distinct keys decoded
+    uint64_t last_batch[3] = {0, 0, 0};  // wave batch check: groups formed, rejected, items re-checked
+    // nwv_bls_set_wave_batch_min: large wave calls of at least this many items take the wave batch
+    // check (0: never)
+    std::atomic<size_t> wave_batch_min{0};
 };
 // the BLS engine's state of one context: one BlsDev per device of the context (nwv_init with
 // several devices shards nwv_bls_verify_many by item index, bls_shard.h).  Diagnostic / test hook:
@@ -1345,6 +1491,16 @@ int verify_on(BlsDev& d, size_t n_keys, const uint8_t* keys, size_t n, const uin
         return e ? (size_t)std::strtoul(e, nullptr, 10) : (size_t)1024;
     }();
     const bool wave_small = wavem && n <= wave_max;
+    // the wave batch check (one final exponentiation per group of wb_grp items): large wave calls
+    // of at least nwv_bls_set_wave_batch_min items
+    static const size_t wb_grp = [] {
+        const char* e = std::getenv("NWV_BLS_BATCH_GROUP");
+        const size_t v = e ? (size_t)std::strtoul(e, nullptr, 10) : (size_t)NWV_BLS_BATCH_GROUP_DEFAULT;
+        return v < 1 ? (size_t)1 : v > 4096 ? (size_t)4096 : v;
+    }();
+    const size_t wb_min = d.wave_batch_min.load(std::memory_order_relaxed);
+    const bool wbatch = wavem && !wave_small && wb_min > 0 && n >= wb_min;
+    const size_t wb_ng = wbatch ? (n + wb_grp - 1) / wb_grp : 0, wb_m = wbatch ? n + wb_ng : 0;
     int rc;
     // the call's key table: cache slots (lookups only) or scratch entries KC_CAP + j
     std::shared_lock<std::shared_mutex> kc_hold(d.kc.mu);  // records stay put while our kernels read them
@@ -1408,7 +1564,7 @@ int verify_on(BlsDev& d, size_t n_keys, const uint8_t* keys, size_t n, const uin
                  o_moff = a.add(msg_off, 8 * n), o_mlen = a.add(msg_len, 4 * n), o_dst = a.add(dst, dl),
                  o_seed = a.add(seed, 32), o_kmode = a.add(kside ? (const void*)kmode.data() : zero, 4 * kmode.size() + 4),
                  o_scs = a.add(keep ? (const void*)kept.slots.data() : zero, 4 * kept.slots.size() + 4);
-    if ((rc = L.stage.ensure(al256(a.total) + 64)) || (rc = L.in.ensure(a.total))) return rc;
+    if ((rc = L.stage.ensure(al256(a.total) + 64 + 4 * wb_ng)) || (rc = L.in.ensure(a.total))) return rc;
     uint8_t* h = static_cast<uint8_t*>(L.stage.p);
     for (size_t k = 0; k < a.parts.size(); k++)
         if (a.parts[k].second) std::memcpy(h + a.offs[k], a.parts[k].first, a.parts[k].second);
@@ -1423,7 +1579,13 @@ int verify_on(BlsDev& d, size_t n_keys, const uint8_t* keys, size_t n, const uin
                  w_hh = al256(w_prec + 4 * G1J_REC_WORDS * (batch ? n + 1 : 0) + 4),
                  w_sdec = al256(w_hh + 4 * G1H_REC_WORDS * (wavem ? n : 0)), w_ssub = al256(w_sdec + 4 * n),
                  w_spair = al256(w_ssub + 4 * n), w_aj = al256(w_spair + 4 * n + 4),
-                 w_end = w_aj + 4 * G2J_WORDS * (wavem ? n : 0) + 4;
+                 w_wb = al256(w_aj + 4 * G2J_WORDS * (wavem ? n + wb_ng : 0) + 4),
+                 // the wave batch check's scratch: F records, [r] H, [r] sig, the groups' S_g, in-batch
+                 // flags, the groups' verdict words
+                 w_wf = w_wb, w_wp = al256(w_wf + 4 * FB_REC_WORDS * wb_m), w_wj = al256(w_wp + 4 * G1H_REC_WORDS * wb_m),
+                 w_wsg = al256(w_wj + 4 * G1J_REC_WORDS * (wbatch ? n : 0)),
+                 w_winb = al256(w_wsg + 4 * G1_REC_WORDS * wb_ng), w_wgok = al256(w_winb + 4 * (wbatch ? n : 0)),
+                 w_end = w_wgok + 4 * wb_ng + 4;
     if ((rc = L.work.ensure(w_end))) return rc;
     uint8_t* in = static_cast<uint8_t*>(L.in.p);
     uint8_t* w = static_cast<uint8_t*>(L.work.p);
@@ -1457,6 +1619,7 @@ int verify_on(BlsDev& d, size_t n_keys, const uint8_t* keys, size_t n, const uin
     bool untimed = false;  // a small call that recorded no stage events (set on that path only)
     auto trec = [&](int k, hipStream_t s) { return no_timing ? hipSuccess : hipEventRecord(L.ev[k], s); };
     // stage times of the completed call, its path and key counts -> the device's "last call"
+    uint64_t wb_stat[3] = {0, 0, 0};
     auto finish = [&](int path_done) -> int {
         const int pairs[5][2] = {{0, 1}, {3, 4}, {5, 6}, {1, 2}, {7, 8}};  // keys, sigs, h2c, apk, pairing
         double ms5[5] = {0, 0, 0, 0, 0};
@@ -1470,6 +1633,7 @@ int verify_on(BlsDev& d, size_t n_keys, const uint8_t* keys, size_t n, const uin
         d.last_path = path_done;
         d.last_keys[0] = hits;
         d.last_keys[1] = n_dec;
+        std::memcpy(d.last_batch, wb_stat, sizeof wb_stat);
         return NWV_OK;
     };
     BLS_HIP(nwv_stage::stage_h2d(in, h, a.total, s0));  // small calls: through kernel arguments
@@ -1591,20 +1755,87 @@ int verify_on(BlsDev& d, size_t n_keys, const uint8_t* keys, size_t n, const uin
             const char* e = std::getenv("NWV_BLS_LDS_PAD");
             return e ? (size_t)std::strtoull(e, nullptr, 10) : (size_t)0;
         }();
-        if (pack > 1 && ensure_pair_script()) return NWV_ERR_HIP;
-        if (pack > 1)
-            hipLaunchKernelGGL(k_blsw_pair_k, dim3((unsigned)((n + pack - 1) / pack)), dim3(64),
+        if ((pack > 1 || wbatch) && ensure_pair_script()) return NWV_ERR_HIP;
+        const auto* d_off = reinterpret_cast<const uint32_t*>(in + o_off);
+        const auto* d_cnt = reinterpret_cast<const uint32_t*>(in + o_cnt);
+        const auto* d_idx = reinterpret_cast<const uint32_t*>(in + o_idx);
+        // the per-item pairing checks of items [lo, lo + m): every item's own final exponentiation
+        auto per_item_range = [&](size_t lo, size_t m) {
+            if (pack > 1)
+                hipLaunchKernelGGL(k_blsw_pair_k, dim3((unsigned)((m + pack - 1) / pack)), dim3(64),
+                                   (size_t)4 * (wave::KP_WORDS + pack * wave::SW * wave::NSLOTS_PC) + lds_pad, s0,
+                                   (uint32_t)m, pack, (const uint32_t*)srec + G1_REC_WORDS * lo,
+                                   (const int32_t*)sdec + lo, (const uint32_t*)hrec + G1_REC_WORDS * lo, 0,
+                                   (const uint32_t*)ajrec + G2J_WORDS * lo, (const int32_t*)sapk + lo, kt, d_off + lo,
+                                   d_cnt + lo, d_idx, km ? km + lo : nullptr, spair + lo);
+            else
+                hipLaunchKernelGGL(k_blsw_pair, dim3((unsigned)m), dim3(64), lds_pad, s0, (uint32_t)m,
+                                   (const uint32_t*)srec + G1_REC_WORDS * lo, (const int32_t*)sdec + lo,
+                                   (const uint32_t*)hrec + G1_REC_WORDS * lo, 0, (const uint32_t*)ajrec + G2J_WORDS * lo,
+                                   (const int32_t*)sapk + lo, kt, d_off + lo, d_cnt + lo, d_idx,
+                                   km ? km + lo : nullptr, spair + lo);
+        };
+        int path_done = 3;
+        if (wbatch) {
+            auto* wf = reinterpret_cast<uint32_t*>(w + w_wf);
+            auto* wp = reinterpret_cast<uint32_t*>(w + w_wp);
+            auto* wj = reinterpret_cast<uint32_t*>(w + w_wj);
+            auto* wsg = reinterpret_cast<uint32_t*>(w + w_wsg);
+            auto* winb = reinterpret_cast<uint32_t*>(w + w_winb);
+            auto* wgok = reinterpret_cast<int32_t*>(w + w_wgok);
+            const uint32_t G = (uint32_t)wb_grp, ng = (uint32_t)wb_ng, gmax = (uint32_t)std::min<size_t>(wb_grp, n);
+            BLS_HIP(hipMemsetAsync(wgok, 0, 4 * wb_ng, s0));  // a group whose tree does not finish stays rejected
+            hipLaunchKernelGGL(k_blsw_rlc_pts, dim3(kBlocks(2 * n)), dim3(BLS_LANES), 0, s0, (uint32_t)n,
+                               (const uint32_t*)srec, (const uint32_t*)hrec, (const int32_t*)sdec, (const int32_t*)sapk, km,
+                               (const uint8_t*)(in + o_seed), wp, wj, winb, spair);
+            for (uint32_t m = gmax; m > 1; m = (m + 1) / 2)
+                hipLaunchKernelGGL(k_blsw_sfold, dim3(kBlocks((size_t)ng * ((m + 1) / 2))), dim3(BLS_LANES), 0, s0,
+                                   (uint32_t)n, G, ng, m, wj);
+            hipLaunchKernelGGL(k_blsw_sig_items, dim3(kBlocks(ng)), dim3(BLS_LANES), 0, s0, (uint32_t)n, G, ng,
+                               (const uint32_t*)wj, wsg, wp, ajrec);
+            const MillArgs ma{(uint32_t)n, wsg, winb, wf};
+            hipLaunchKernelGGL(k_blsw_mill_k, dim3((unsigned)((wb_m + pack - 1) / pack)), dim3(64),
                                (size_t)4 * (wave::KP_WORDS + pack * wave::SW * wave::NSLOTS_PC) + lds_pad, s0,
-                               (uint32_t)n, pack, (const uint32_t*)srec, (const int32_t*)sdec, (const uint32_t*)hrec, 0,
-                               (const uint32_t*)ajrec, (const int32_t*)sapk, kt,
-                               reinterpret_cast<const uint32_t*>(in + o_off), reinterpret_cast<const uint32_t*>(in + o_cnt),
-                               reinterpret_cast<const uint32_t*>(in + o_idx), km, spair);
-        else
-            hipLaunchKernelGGL(k_blsw_pair, dim3((unsigned)n), dim3(64), lds_pad, s0, (uint32_t)n, (const uint32_t*)srec,
-                               (const int32_t*)sdec, (const uint32_t*)hrec, 0, (const uint32_t*)ajrec,
-                               (const int32_t*)sapk, kt, reinterpret_cast<const uint32_t*>(in + o_off),
-                               reinterpret_cast<const uint32_t*>(in + o_cnt), reinterpret_cast<const uint32_t*>(in + o_idx),
-                               km, spair);
+                               (uint32_t)wb_m, pack, ma, (const uint32_t*)wp, (const uint32_t*)ajrec, kt, d_off, d_cnt,
+                               d_idx, km);
+            for (uint32_t s = 1;; s *= WB_FAN) {
+                const uint32_t ents = (gmax + 1 + s - 1) / s, wpg = (ents + WB_FAN - 1) / WB_FAN;
+                hipLaunchKernelGGL(k_blsw_ffold, dim3(ng * wpg), dim3(64), 0, s0, (uint32_t)n, G, wpg, s,
+                                   wpg == 1 ? 1 : 0, wf, wgok);
+                if (wpg == 1) break;
+            }
+            hipLaunchKernelGGL(k_blsw_mark, dim3(kBlocks(n)), dim3(BLS_LANES), 0, s0, (uint32_t)n, G,
+                               (const int32_t*)wgok, (const uint32_t*)winb, spair);
+            BLS_HIP(hipGetLastError());
+            int32_t* hgok = reinterpret_cast<int32_t*>(h + al256(a.total) + 64);  // pinned: the groups' verdicts
+            BLS_HIP(hipMemcpyAsync(hgok, wgok, 4 * wb_ng, hipMemcpyDeviceToHost, s0));
+            BLS_HIP(hipStreamSynchronize(s0));
+            // every rejected group's items per item.  A launch over a few items costs one item's
+            // whole chain (~3 ms) however few they are, so rejected groups less than WB_GAP items
+            // apart share a launch with the accepted groups between them (~1 us an item there)
+            constexpr size_t WB_GAP = 1024;
+            wb_stat[0] = wb_ng;
+            for (size_t g = 0; g < wb_ng;) {
+                if (hgok[g] == 1) {
+                    g++;
+                    continue;
+                }
+                size_t e = g + 1;  // the range's end: past its last rejected group
+                wb_stat[1]++;
+                for (size_t q = e; q < wb_ng && (q - e) * wb_grp < WB_GAP; q++)
+                    if (hgok[q] != 1) {
+                        e = q + 1;
+                        wb_stat[1]++;
+                    }
+                const size_t lo = g * wb_grp, hi = std::min(n, e * wb_grp);
+                per_item_range(lo, hi - lo);
+                wb_stat[2] += hi - lo;
+                g = e;
+            }
+            path_done = wb_stat[1] ? 5 : 4;
+        } else {
+            per_item_range(0, n);
+        }
         BLS_HIP(hipEventRecord(L.ev[8], s0));
         hipLaunchKernelGGL(k_blsw_status, dim3(kBlocks(n)), dim3(BLS_LANES), 0, s0, (uint32_t)n,
                            (const int32_t*)sdec, (const int32_t*)ssub, (const int32_t*)sapk, (const int32_t*)spair, st,
@@ -1612,7 +1843,7 @@ int verify_on(BlsDev& d, size_t n_keys, const uint8_t* keys, size_t n, const uin
         BLS_HIP(hipGetLastError());
         BLS_HIP(hipMemcpyAsync(status, st, 4 * n, hipMemcpyDeviceToHost, s0));
         BLS_HIP(hipStreamSynchronize(s0));
-        return finish(3);
+        return finish(path_done);
     }
     // main: signatures, then the join
     BLS_HIP(hipEventRecord(L.ev[3], s0));
@@ -1764,6 +1995,30 @@ int nwv_bls_last_path(nwv_ctx* ctx) {
     if (rc) return rc;
     std::lock_guard<std::mutex> g(d->stat_mu);
     return d->last_path;
+}
+
+int nwv_bls_set_wave_batch_min(nwv_ctx* ctx, size_t n) {
+    BlsCtx* c;
+    int rc = ctx_of(ctx, &c);
+    if (rc) return rc;
+    for (BlsDev* d : c->devs) d->wave_batch_min.store(n, std::memory_order_relaxed);
+    return NWV_OK;
+}
+
+size_t nwv_bls_wave_batch_min(const nwv_ctx* ctx) {
+    BlsCtx* c;
+    if (ctx_of(const_cast<nwv_ctx*>(ctx), &c)) return 0;
+    return c->devs[0]->wave_batch_min.load(std::memory_order_relaxed);
+}
+
+int nwv_bls_last_batch(nwv_ctx* ctx, uint64_t out[3]) {
+    if (!out) return nwv_internal_set_err(NWV_ERR_ARG, "null argument");
+    BlsDev* d;
+    int rc = last_dev_of(ctx, &d);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> g(d->stat_mu);
+    for (int k = 0; k < 3; k++) out[k] = d->last_batch[k];
+    return NWV_OK;
 }
 
 int nwv_bls_last_keys(nwv_ctx* ctx, uint64_t out[2]) {

@@ -333,6 +333,9 @@ extern "C" {
     ) -> c_int;
     pub fn nwv_bls_last_kernel_ms(ctx: *mut NwvCtx, out_ms: *mut f64) -> c_int;
     pub fn nwv_bls_last_path(ctx: *mut NwvCtx) -> c_int;
+    pub fn nwv_bls_set_wave_batch_min(ctx: *mut NwvCtx, n: usize) -> c_int;
+    pub fn nwv_bls_wave_batch_min(ctx: *const NwvCtx) -> usize;
+    pub fn nwv_bls_last_batch(ctx: *mut NwvCtx, out: *mut u64) -> c_int;
     pub fn nwv_bls_last_keys(ctx: *mut NwvCtx, out: *mut u64) -> c_int;
     pub fn nwv_bls_keycache_register(ctx: *mut NwvCtx, n_keys: usize, keys: *const u8) -> c_int;
     pub fn nwv_bls_keycache_reset(ctx: *mut NwvCtx) -> c_int;
