@@ -93,6 +93,46 @@ int nwv_bls_last_batch(nwv_ctx* ctx, uint64_t out[3]);
  * out[1] distinct keys the call decoded itself */
 int nwv_bls_last_keys(nwv_ctx* ctx, uint64_t out[2]);
 
+/* The message ring (per device): hashed message points kept by (dst, message), so a message that
+ * recurs -- the votes for a header and the certificate built from them sign one 32-byte digest
+ * (types/src/primary.rs:351-364, :594-607) -- is hashed to G1 once, and a message known ahead of
+ * its signature (a certificate's digest is a function of its header) can be hashed before the
+ * call that needs it.  Opt-in: slots = 0 (the default) means no lookups and no publishes, and
+ * every call takes exactly the launches it takes without this setting.  The first non-zero value
+ * allocates `slots` records (172 bytes each, at most 65,536) on every BLS device object; a later
+ * different non-zero value is NWV_ERR_ARG (the buffer never moves); a later 0 switches lookups and
+ * publishes off.  Only calls on the small wave path use the ring (at most NWV_BLS_WAVE_MAX and at
+ * most 1,024 items, neither NWV_FLAG_BLS_BATCH nor NWV_FLAG_BLS_PER_ITEM), and only messages of at
+ * most 64 bytes under a DST of at most 64 bytes are kept.  Statuses never depend on the ring. */
+int nwv_bls_set_msg_ring(nwv_ctx* ctx, size_t slots);
+size_t nwv_bls_msg_ring(const nwv_ctx* ctx);
+/* hash n messages into the ring of EVERY BLS device object (placement may send the later call to
+ * any of them); messages the ring holds, duplicates and messages over 64 bytes are skipped.
+ * NWV_OK and nothing done when the ring is off.  dst = NULL selects NWV_BLS_DST. */
+int nwv_bls_hash_ahead(nwv_ctx* ctx, size_t n, const uint8_t* msg_base, const uint64_t* msg_off,
+                       const uint32_t* msg_len, const uint8_t* dst, size_t dst_len);
+/* nwv_bls_verify_many that also hashes n_ahead messages ahead_base[ahead_off[j] .. + ahead_len[j])
+ * into the ring, beside the call's own work (its critical path does not wait for them).  Ahead
+ * message j is kept only if ahead_gate[j] == UINT32_MAX or status[ahead_gate[j]] == NWV_BLS_OK
+ * (ahead_gate = NULL: no gates), so a forged header does not fill the ring.  Statuses are exactly
+ * those of nwv_bls_verify_many; with the ring off, or on a call that does not use it, the ahead
+ * list is ignored. */
+int nwv_bls_verify_many_ahead(nwv_ctx* ctx, size_t n_keys, const uint8_t* keys, size_t n, const uint8_t* sigs,
+                              const uint32_t* pk_off, const uint32_t* pk_cnt, const uint32_t* pk_idx,
+                              const uint8_t* msg_base, const uint64_t* msg_off, const uint32_t* msg_len,
+                              const uint8_t* dst, size_t dst_len, int32_t* status, size_t n_ahead,
+                              const uint8_t* ahead_base, const uint64_t* ahead_off, const uint32_t* ahead_len,
+                              const uint32_t* ahead_gate);
+/* the ring's part in the calling thread's last verify call on this context: out[0] hits whose
+ * record was copied (items whose keys are all in the key cache), out[1] hits that ran the h_eff
+ * chain on the record, out[2] hashes computed, out[3] slots published for the call's own
+ * messages, out[4] ahead messages published.  All zero when the call did not use the ring. */
+int nwv_bls_last_msgs(nwv_ctx* ctx, uint64_t out[5]);
+/* slot counts of the ring of the device that served the calling thread's last verify call:
+ * out[0] held (published under a message), out[1] busy (reserved by a call in flight), out[2]
+ * pinned (read by a call in flight) */
+int nwv_bls_msg_ring_stats(nwv_ctx* ctx, uint64_t out[3]);
+
 /* The committee key cache (per device).  fastcrypto decodes and validates a public key once, at
  * deserialization; nwv_bls_keycache_register does that once per device for the committee's keys
  * (epoch start, Core::change_epoch primary/src/core.rs:592-611) and keeps the records of the keys

@@ -31,7 +31,16 @@ _SIGS = {
     "nwv_bls_keycache_register": ([_vp, _sz, _vp], _i32),
     "nwv_bls_keycache_reset": ([_vp], _i32),
     "nwv_bls_keycache_size": ([_vp], _i32),
+    "nwv_bls_set_msg_ring": ([_vp, _sz], _i32),
+    "nwv_bls_msg_ring": ([_vp], _sz),
+    "nwv_bls_hash_ahead": ([_vp, _sz, _vp, _vp, _vp, _vp, _sz], _i32),
+    "nwv_bls_verify_many_ahead": ([_vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp,
+                                   _sz, _vp, _vp, _vp, _vp], _i32),
+    "nwv_bls_last_msgs": ([_vp, _vp], _i32),
+    "nwv_bls_msg_ring_stats": ([_vp, _vp], _i32),
 }
+MSG_COUNTERS = ("hits_copied", "hits_chained", "computed", "published", "ahead_published")
+NO_GATE = 0xFFFFFFFF
 KERNELS = ("keys_new_to_cache", "sig_decode", "hash_to_g1", "key_sums", "pairing_check")
 PATHS = ("per_item", "batch_accepted", "batch_rejected_then_per_item", "wave", "wave_batch_accepted",
          "wave_batch_rejected_then_per_item")
@@ -42,8 +51,11 @@ def _bind(lib):
     if id(lib) in _bound:
         return lib
     for name, (args, res) in _SIGS.items():
-        f = getattr(lib, name)
-        f.argtypes, f.restype = args, res
+        # (an older build selected with NWV_LIB for an A/B run lacks the newest entry points:
+        # calling one of them there still raises)
+        f = getattr(lib, name, None)
+        if f is not None:
+            f.argtypes, f.restype = args, res
     _bound.add(id(lib))
     return lib
 
@@ -91,6 +103,53 @@ class Bls:
             idx.ctypes.data, arena.ctypes.data, offs.ctypes.data, lens.ctypes.data, dst,
             len(dst) if dst else 0, st.ctypes.data))
         return st[:n]
+
+    def verify_many_ahead(self, keys, sigs, key_lists, msgs, ahead, gates=None, dst=None):
+        """verify_many that also hashes the messages `ahead` into the message ring; ahead[j] is kept
+        only if item gates[j] verifies (NO_GATE, or gates=None: kept anyway)"""
+        n = len(sigs)
+        kb = _arr(b"".join(keys))
+        sg = _arr(b"".join(sigs))
+        cnt = np.array([len(k) for k in key_lists], dtype=np.uint32)
+        off = np.zeros(n, dtype=np.uint32)
+        if n > 1:
+            off[1:] = np.cumsum(cnt[:-1], dtype=np.uint32)
+        idx = np.array([k for ks in key_lists for k in ks] or [0], dtype=np.uint32)
+        arena, offs, lens = _msgs(msgs)
+        a_arena, a_offs, a_lens = _msgs(ahead)
+        g = np.array(list(gates) if gates is not None else [NO_GATE] * len(ahead), dtype=np.uint32)
+        st = np.zeros(max(1, n), dtype=np.int32)
+        _lib._check(self.lib.nwv_bls_verify_many_ahead(
+            self._h, len(keys), kb.ctypes.data, n, sg.ctypes.data, off.ctypes.data, cnt.ctypes.data,
+            idx.ctypes.data, arena.ctypes.data, offs.ctypes.data, lens.ctypes.data, dst,
+            len(dst) if dst else 0, st.ctypes.data, len(ahead), a_arena.ctypes.data, a_offs.ctypes.data,
+            a_lens.ctypes.data, g.ctypes.data))
+        return st[:n]
+
+    # the message ring (hashed message points kept per device): off at 0
+    def set_msg_ring(self, slots):
+        _lib._check(self.lib.nwv_bls_set_msg_ring(self._h, slots))
+
+    def msg_ring(self):
+        return int(self.lib.nwv_bls_msg_ring(self._h))
+
+    def hash_ahead(self, msgs, dst=None):
+        """hash the messages into every device's ring ahead of the calls that verify over them"""
+        arena, offs, lens = _msgs(msgs)
+        _lib._check(self.lib.nwv_bls_hash_ahead(self._h, len(msgs), arena.ctypes.data, offs.ctypes.data,
+                                                lens.ctypes.data, dst, len(dst) if dst else 0))
+
+    def last_msgs(self):
+        """{counter: count} of the ring's part in this thread's last verify call (MSG_COUNTERS)"""
+        out = np.zeros(5, dtype=np.uint64)
+        _lib._check(self.lib.nwv_bls_last_msgs(self._h, out.ctypes.data))
+        return dict(zip(MSG_COUNTERS, (int(x) for x in out)))
+
+    def msg_ring_stats(self):
+        """(held, busy, pinned) slots of the ring that served this thread's last verify call"""
+        out = np.zeros(3, dtype=np.uint64)
+        _lib._check(self.lib.nwv_bls_msg_ring_stats(self._h, out.ctypes.data))
+        return int(out[0]), int(out[1]), int(out[2])
 
     def verify_many_arrays(self, keys, sigs, pk_off, pk_cnt, pk_idx, arena, offs, lens, status, dst=None):
         """the same over prepared numpy arrays (bench / large batches)"""

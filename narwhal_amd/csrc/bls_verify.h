@@ -308,9 +308,20 @@ NWV_HD bool w_pairing_check(const W& w, const uint32_t* sig_rec, const uint32_t*
 // fraction: no inversion); the two isogeny maps (homogeneous), their sum and [h_eff] run as
 // stage programs.  out: X, Y, Z (x = X / Z, y = Y / Z) and an identity flag (3 NL + 1 words).
 constexpr int G1H_REC_WORDS = 3 * NL + 1;
+// U as a homogeneous record: X, Y, Z and the identity flag
+template <class W>
+NWV_HD void w_g1h_store(const W& w, uint32_t* out) {
+    using namespace wave;
+    w.get_words(REG_U, out, 3);
+    w.sync();
+    const bool inf = fp_is_zero(w.get(REG_U + 2));
+    w.lanes(1, [&](int) { out[3 * NL] = inf ? 1u : 0u; });
+}
+// raw_out (optional): the RAW record, the sum of the two maps before [h_eff], written before the
+// chain runs -- what the message ring keeps (with clear = false it equals `out`)
 template <class W>
 NWV_HD void w_hash_to_g1(const W& w, const uint8_t* msg, uint32_t n, const uint8_t* dst, uint32_t dl, uint32_t* out,
-                         bool clear = true) {
+                         bool clear = true, uint32_t* raw_out = nullptr) {
     using namespace wave;
     init_slots(w);
     w.lanes(2, [&](int j) {
@@ -325,11 +336,43 @@ NWV_HD void w_hash_to_g1(const W& w, const uint8_t* msg, uint32_t n, const uint8
     });
     w.sync();
     w.run(P_ISO2_ADD);
+    if (raw_out) {
+        w_g1h_store(w, raw_out);
+        w.sync();
+    }
     if (clear) g1_chain(w, BLS_H_EFF);  // (else U holds the sum of the two maps)
-    w.get_words(REG_U, out, 3);
+    w_g1h_store(w, out);
+}
+// [h_eff] of a stored raw record (w_hash_to_g1's raw_out): the chain alone, out as
+// w_hash_to_g1(clear = true) writes it
+template <class W>
+NWV_HD void w_g1_clear_raw(const W& w, const uint32_t* raw, uint32_t* out) {
+    using namespace wave;
+    init_slots(w);
+    w.put_words(REG_U, raw, 3);
+    w.put_words(REG_V, raw, 3);
     w.sync();
-    const bool inf = fp_is_zero(w.get(REG_U + 2));
-    w.lanes(1, [&](int) { out[3 * NL] = inf ? 1u : 0u; });
+    g1_chain(w, BLS_H_EFF);
+    w_g1h_store(w, out);
+}
+// The hash role of one item of a call that uses the message ring (k_blsw_pre_r).  src: the ring
+// record of the item's message, or null (a miss); pub: the ring record a miss also fills, or null;
+// key_side: the item takes the raw form (its keys carry h_eff), else the cleared one.
+//   hit,  key side : out <- the record            hit,  else : out <- [h_eff] record
+//   miss, key side : out <- raw (pub <- raw)      miss, else : pub <- raw, then out <- [h_eff] raw
+template <class W>
+NWV_HD void w_hash_ring_item(const W& w, const uint8_t* msg, uint32_t n, const uint8_t* dst, uint32_t dl,
+                             const uint32_t* src, uint32_t* pub, bool key_side, uint32_t* out) {
+    if (!src) {
+        w_hash_to_g1(w, msg, n, dst, dl, out, !key_side, pub);
+        return;
+    }
+    if (key_side)
+        w.lanes(64, [&](int j) {
+            for (int t = j; t < G1H_REC_WORDS; t += 64) out[t] = src[t];
+        });
+    else
+        w_g1_clear_raw(w, src, out);
 }
 
 // the signature's G1 membership on a wave (sig_decode's g1_in_group): [x^2] P = -phi(P) with

@@ -36,6 +36,7 @@
 #include "../../include/nwv_bls.h"
 #include "bls_verify.h"
 #include "bls_shard.h"
+#include "bls_msg_ring.h"
 #include "place.h"
 #include "stage_args.h"
 
@@ -913,6 +914,45 @@ __global__ __launch_bounds__(64) void k_blsw_pre(uint32_t n, const uint8_t* msg,
     else if (b < 2 * n)
         blsw_apk_item(lds, b - n, kt, pk_off, pk_cnt, pk_idx, kmode, arec, st_apk);
 }
+// k_blsw_pre of a call that uses the device's message ring (bls_msg_ring.h; `ring`: G1H_REC_WORDS
+// u32 a slot, raw hashed points).  hsrc[i]: the slot that holds item i's message (a hit: no
+// hashing, the record copied for a key-side item, run through the h_eff chain otherwise) or
+// MR_NONE; hpub[i]: the slot a miss also writes its raw point to, or MR_NONE.  Items of one call
+// that share a missing message each compute on their own (no cross-block wait); the host gives
+// only the first of them a slot.  The host keeps every slot named here away from other calls'
+// writes until this call's stream has completed (pins, busy flags).
+constexpr uint32_t MR_NONE = 0xffffffffu;
+__global__ __launch_bounds__(64) void k_blsw_pre_r(uint32_t n, const uint8_t* msg, const uint64_t* off,
+                                                   const uint32_t* len, const uint8_t* dst, uint32_t dl, uint32_t* hrec,
+                                                   KeyTab kt, const uint32_t* pk_off, const uint32_t* pk_cnt,
+                                                   const uint32_t* pk_idx, const uint32_t* kmode, uint32_t* arec,
+                                                   int32_t* st_apk, uint32_t* ring, const uint32_t* hsrc,
+                                                   const uint32_t* hpub) {
+    constexpr int LW = wave::WM_WORDS > 32 * G2J_WORDS ? wave::WM_WORDS : 32 * G2J_WORDS;
+    __shared__ uint32_t lds[LW];
+    const uint32_t b = blockIdx.x;
+    if (b < n) {
+        const wave::Wave w{lds + wave::KP_WORDS, (int)threadIdx.x};
+        const uint32_t src = hsrc[b], pub = hpub[b];
+        w_hash_ring_item(w, msg + off[b], len[b], dst, dl,
+                         src != MR_NONE ? ring + (size_t)G1H_REC_WORDS * src : nullptr,
+                         pub != MR_NONE ? ring + (size_t)G1H_REC_WORDS * pub : nullptr, kmode && kmode[b],
+                         hrec + (size_t)G1H_REC_WORDS * b);
+    } else if (b < 2 * n) {
+        blsw_apk_item(lds, b - n, kt, pk_off, pk_cnt, pk_idx, kmode, arec, st_apk);
+    }
+}
+// hashing ahead of need: one wave per message, the raw point alone, into the message's reserved
+// ring slot
+__global__ __launch_bounds__(64) void k_blsw_h2c_ahead(uint32_t n, const uint8_t* msg, const uint64_t* off,
+                                                       const uint32_t* len, const uint8_t* dst, uint32_t dl,
+                                                       uint32_t* ring, const uint32_t* slot) {
+    BLSW_LDS(wave::NSLOTS);
+    const uint32_t i = blockIdx.x;
+    if (i >= n) return;
+    const wave::Wave w{wm, (int)threadIdx.x};
+    w_hash_to_g1(w, msg + off[i], len[i], dst, dl, ring + (size_t)G1H_REC_WORDS * slot[i], false);
+}
 
 // AggregateAuthenticator::aggregate (types/src/primary.rs:476-477) on the wave engine: a wave adds
 // up to 16 points with the smallest g1_sum program that holds them (2, 4, 8, 16 inputs: one level
@@ -1191,11 +1231,67 @@ struct SigSlots {
 
 constexpr size_t kMaxLanes = 8;
 
+// The hashed message points of a device (nwv_bls_set_msg_ring; bls_msg_ring.h keeps the books).
+// Small wave calls look their messages up, pin the hits and reserve a slot per distinct miss
+// before their kernels run; k_blsw_pre_r reads the pinned records and fills the reserved ones; the
+// call publishes and unpins after its streams have synchronised.  No lock is held meanwhile.
+struct BlsMsgCache {
+    nwv::BlsMsgRing ring;
+    DBuf rec;                     // ring.cap() x G1H_REC_WORDS u32: raw points
+    std::atomic<bool> on{false};  // lookups and publishes (the buffer, once there, stays)
+};
+// a call's ring slots: the hits it pinned and the slots it reserved (for its own misses and for its
+// ahead messages).  finish() publishes and unpins after the call's streams have synchronised; a
+// call that fails before that synchronises them here and gives everything back, and if that wait
+// fails too the slots stay pinned / busy (abandoned, as SigSlots does).
+struct MsgSlots {
+    struct Fresh {
+        uint32_t slot;
+        nwv::MsgKey key;
+        uint32_t gate;  // ahead messages: the item whose OK status lets it publish, or UINT32_MAX
+        bool ahead;
+    };
+    nwv::BlsMsgRing* ring = nullptr;
+    std::vector<uint32_t> pinned;
+    std::vector<Fresh> fresh;
+    hipStream_t streams[2] = {nullptr, nullptr};
+    // status: the call's per-item statuses (null: no gates to read).  out[3] += published item
+    // slots, out[4] += published ahead slots
+    void finish(const int32_t* status, uint64_t* out) {
+        if (!ring) return;
+        for (const Fresh& f : fresh) {
+            if (f.ahead && f.gate != UINT32_MAX && (!status || status[f.gate] != ST_OK)) {
+                ring->release(f.slot);
+                continue;
+            }
+            if (ring->publish(f.slot, f.key) == f.slot && out) out[f.ahead ? 4 : 3]++;
+        }
+        for (uint32_t s : pinned) ring->unpin(s);
+        ring = nullptr;
+    }
+    ~MsgSlots() {
+        if (!ring) return;
+        for (hipStream_t s : streams)
+            if (s && hipStreamSynchronize(s) != hipSuccess) return;  // abandoned, see above
+        for (const Fresh& f : fresh) ring->release(f.slot);
+        for (uint32_t s : pinned) ring->unpin(s);
+    }
+};
+// a call's ahead messages (nwv_bls_verify_many_ahead)
+struct Ahead {
+    size_t n = 0;
+    const uint8_t* base = nullptr;
+    const uint64_t* off = nullptr;
+    const uint32_t* len = nullptr;
+    const uint32_t* gate = nullptr;
+};
+
 struct BlsDev {
     int ordinal = -1;
     uint32_t flags = 0;  // the context's nwv_init flags
     BlsKeyCache kc;
     BlsSigCache sc;
+    BlsMsgCache mr;
     std::mutex pool_mu;
     std::condition_variable pool_cv;
     std::vector<std::unique_ptr<BlsLane>> lanes;
@@ -1474,7 +1570,7 @@ int keycache_register(BlsDev& d, size_t n_keys, const uint8_t* keys) {
 int verify_on(BlsDev& d, size_t n_keys, const uint8_t* keys, size_t n, const uint8_t* sigs, const uint32_t* pk_off,
               const uint32_t* pk_cnt, const uint32_t* pk_idx, size_t n_idx, const uint8_t* msg_base,
               const uint64_t* msg_off, const uint32_t* msg_len, size_t msg_bytes, const uint8_t* dst, size_t dl,
-              int32_t* status) {
+              int32_t* status, const Ahead* ahead = nullptr, uint64_t* mstat = nullptr) {
     LaneLease lane(d);
     if (lane.rc()) return lane.rc();
     BlsLane& L = *lane;
@@ -1553,6 +1649,80 @@ int verify_on(BlsDev& d, size_t n_keys, const uint8_t* keys, size_t n, const uin
         kept.sc = &d.sc;
         kept.n = n;
     }
+    // the device's message ring (the same small wave calls): hits pinned, one slot reserved per
+    // distinct missing message and per ahead message that is neither cached nor a duplicate
+    const bool use_ring = wave_small && n <= 1024 && d.mr.on.load(std::memory_order_acquire) &&
+                          dl <= nwv::MsgKey::MAX_DST;
+    MsgSlots ms;
+    std::vector<uint8_t> rsec;  // the ring's arena section: aoff | hsrc | hpub | aslot | alen | ahead messages
+    size_t n_ah = 0, r_hsrc = 0, r_hpub = 0, r_aslot = 0, r_alen = 0, r_amsg = 0;
+    uint64_t mcount[5] = {0, 0, 0, 0, 0};
+    if (use_ring) {
+        nwv::BlsMsgRing& R = d.mr.ring;
+        ms.ring = &R;
+        ms.streams[0] = L.stream;
+        ms.streams[1] = L.side[0];
+        std::vector<uint32_t> hsrc(n, MR_NONE), hpub(n, MR_NONE);
+        std::unordered_multimap<uint64_t, size_t> mine;  // this call's reserved keys: hash -> ms.fresh index
+        auto mine_has = [&](const nwv::MsgKey& k, uint64_t hk) {
+            const auto r = mine.equal_range(hk);
+            for (auto it = r.first; it != r.second; ++it)
+                if (ms.fresh[it->second].key == k) return true;
+            return false;
+        };
+        auto take = [&](const nwv::MsgKey& k, uint32_t gate, bool is_ahead) {
+            const uint64_t hk = k.hash();
+            if (mine_has(k, hk)) return MR_NONE;
+            const uint32_t r = R.reserve();
+            if (r == nwv::BlsMsgRing::NONE) return MR_NONE;  // every slot in use: computed, not kept
+            mine.emplace(hk, ms.fresh.size());
+            ms.fresh.push_back({r, k, gate, is_ahead});
+            return r;
+        };
+        for (size_t i = 0; i < n; i++) {
+            mcount[2]++;
+            if (msg_len[i] > nwv::MsgKey::MAX_MSG) continue;
+            const nwv::MsgKey k = nwv::MsgKey::make(dst, dl, msg_base + msg_off[i], msg_len[i]);
+            const uint32_t s = R.lookup_pin(k);
+            if (s != nwv::BlsMsgRing::NONE) {
+                hsrc[i] = s;
+                ms.pinned.push_back(s);
+                mcount[2]--;
+                mcount[kside && kmode[i] ? 0 : 1]++;
+                continue;
+            }
+            hpub[i] = take(k, UINT32_MAX, false);
+        }
+        std::vector<uint32_t> aslot, alen;
+        std::vector<uint64_t> aoff;
+        std::vector<uint8_t> amsg;
+        for (size_t j = 0; ahead && j < ahead->n; j++) {
+            if (ahead->len[j] > nwv::MsgKey::MAX_MSG) continue;
+            const nwv::MsgKey k = nwv::MsgKey::make(dst, dl, ahead->base + ahead->off[j], ahead->len[j]);
+            if (R.contains(k)) continue;
+            const uint32_t r = take(k, ahead->gate ? ahead->gate[j] : UINT32_MAX, true);
+            if (r == MR_NONE) continue;
+            aslot.push_back(r);
+            alen.push_back(ahead->len[j]);
+            aoff.push_back(amsg.size());
+            amsg.insert(amsg.end(), ahead->base + ahead->off[j], ahead->base + ahead->off[j] + ahead->len[j]);
+        }
+        n_ah = aslot.size();
+        r_hsrc = 8 * n_ah;
+        r_hpub = r_hsrc + 4 * n;
+        r_aslot = r_hpub + 4 * n;
+        r_alen = r_aslot + 4 * n_ah;
+        r_amsg = r_alen + 4 * n_ah;
+        rsec.assign(r_amsg + amsg.size() + 1, 0);
+        if (n_ah) {
+            std::memcpy(rsec.data(), aoff.data(), 8 * n_ah);
+            std::memcpy(rsec.data() + r_aslot, aslot.data(), 4 * n_ah);
+            std::memcpy(rsec.data() + r_alen, alen.data(), 4 * n_ah);
+            if (!amsg.empty()) std::memcpy(rsec.data() + r_amsg, amsg.data(), amsg.size());
+        }
+        std::memcpy(rsec.data() + r_hsrc, hsrc.data(), 4 * n);
+        std::memcpy(rsec.data() + r_hpub, hpub.data(), 4 * n);
+    }
     uint8_t seed[32];
     nwv_internal_fill_seed(nullptr, seed);  // the batch coefficients' key: OS entropy per call
     Arena a;
@@ -1564,6 +1734,8 @@ int verify_on(BlsDev& d, size_t n_keys, const uint8_t* keys, size_t n, const uin
                  o_moff = a.add(msg_off, 8 * n), o_mlen = a.add(msg_len, 4 * n), o_dst = a.add(dst, dl),
                  o_seed = a.add(seed, 32), o_kmode = a.add(kside ? (const void*)kmode.data() : zero, 4 * kmode.size() + 4),
                  o_scs = a.add(keep ? (const void*)kept.slots.data() : zero, 4 * kept.slots.size() + 4);
+    // (one section for everything the ring adds: a single verification still fits stage_h2d's arguments)
+    const size_t o_ring = use_ring ? a.add(rsec.data(), rsec.size()) : 0;
     if ((rc = L.stage.ensure(al256(a.total) + 64 + 4 * wb_ng)) || (rc = L.in.ensure(a.total))) return rc;
     uint8_t* h = static_cast<uint8_t*>(L.stage.p);
     for (size_t k = 0; k < a.parts.size(); k++)
@@ -1652,11 +1824,23 @@ int verify_on(BlsDev& d, size_t n_keys, const uint8_t* keys, size_t n, const uin
                                const_cast<uint32_t*>(kt.rs), const_cast<int32_t*>(kt.ss));
         BLS_HIP(trec(1, s1));
         BLS_HIP(trec(5, s1));
-        hipLaunchKernelGGL(k_blsw_pre, dim3((unsigned)(2 * n)), dim3(64), 0, s1, (uint32_t)n, in + o_msg,
-                           reinterpret_cast<const uint64_t*>(in + o_moff), reinterpret_cast<const uint32_t*>(in + o_mlen),
-                           in + o_dst, (uint32_t)dl, hh, kt, reinterpret_cast<const uint32_t*>(in + o_off),
-                           reinterpret_cast<const uint32_t*>(in + o_cnt), reinterpret_cast<const uint32_t*>(in + o_idx),
-                           km, ajrec, sapk);
+        if (use_ring)
+            hipLaunchKernelGGL(k_blsw_pre_r, dim3((unsigned)(2 * n)), dim3(64), 0, s1, (uint32_t)n, in + o_msg,
+                               reinterpret_cast<const uint64_t*>(in + o_moff),
+                               reinterpret_cast<const uint32_t*>(in + o_mlen), in + o_dst, (uint32_t)dl, hh, kt,
+                               reinterpret_cast<const uint32_t*>(in + o_off),
+                               reinterpret_cast<const uint32_t*>(in + o_cnt),
+                               reinterpret_cast<const uint32_t*>(in + o_idx), km, ajrec, sapk,
+                               static_cast<uint32_t*>(d.mr.rec.p),
+                               reinterpret_cast<const uint32_t*>(in + o_ring + r_hsrc),
+                               reinterpret_cast<const uint32_t*>(in + o_ring + r_hpub));
+        else
+            hipLaunchKernelGGL(k_blsw_pre, dim3((unsigned)(2 * n)), dim3(64), 0, s1, (uint32_t)n, in + o_msg,
+                               reinterpret_cast<const uint64_t*>(in + o_moff),
+                               reinterpret_cast<const uint32_t*>(in + o_mlen), in + o_dst, (uint32_t)dl, hh, kt,
+                               reinterpret_cast<const uint32_t*>(in + o_off),
+                               reinterpret_cast<const uint32_t*>(in + o_cnt),
+                               reinterpret_cast<const uint32_t*>(in + o_idx), km, ajrec, sapk);
         BLS_HIP(trec(2, s1));
         BLS_HIP(trec(6, s1));
         BLS_HIP(trec(3, s0));
@@ -1664,6 +1848,14 @@ int verify_on(BlsDev& d, size_t n_keys, const uint8_t* keys, size_t n, const uin
                            sdec);
         BLS_HIP(trec(4, s0));
         BLS_HIP(hipEventRecord(L.sev[1], s0));
+        // the ahead messages on the main stream, idle from here on: the pairing, on side 0, does
+        // not wait for them
+        if (n_ah)
+            hipLaunchKernelGGL(k_blsw_h2c_ahead, dim3((unsigned)n_ah), dim3(64), 0, s0, (uint32_t)n_ah,
+                               (const uint8_t*)(in + o_ring + r_amsg), reinterpret_cast<const uint64_t*>(in + o_ring),
+                               reinterpret_cast<const uint32_t*>(in + o_ring + r_alen), (const uint8_t*)(in + o_dst),
+                               (uint32_t)dl, static_cast<uint32_t*>(d.mr.rec.p),
+                               reinterpret_cast<const uint32_t*>(in + o_ring + r_aslot));
         kept.stream = s1;  // k_blsw_status writes the ring slots there
         // the rest runs on side 0 behind the hash, which ends after the signatures' decode (one
         // lane each, ~0.45 ms against ~0.57 ms): its wait on the decode is already met, so the
@@ -1690,10 +1882,16 @@ int verify_on(BlsDev& d, size_t n_keys, const uint8_t* keys, size_t n, const uin
         BLS_HIP(hipGetLastError());
         BLS_HIP(hipMemcpyAsync(status, st, 4 * n, hipMemcpyDeviceToHost, s1));
         BLS_HIP(hipStreamSynchronize(s1));
+        if (n_ah) BLS_HIP(hipStreamSynchronize(s0));
         if (keep) {
             d.sc.publish(n, sigs, status, kept.slots);
             kept.sc = nullptr;
         }
+        // H(m) is a function of dst and message alone: a miss is published whatever its item's
+        // status; an ahead message only behind its gate
+        ms.finish(status, mcount);
+        if (mstat)
+            for (int k = 0; k < 5; k++) mstat[k] += mcount[k];
         return finish(3);
     }
     if (!L.side[1] && hipStreamCreateWithFlags(&L.side[1], hipStreamNonBlocking) != hipSuccess)
@@ -1888,6 +2086,67 @@ int verify_on(BlsDev& d, size_t n_keys, const uint8_t* keys, size_t n, const uin
     return finish(path);
 }
 
+// nwv_bls_hash_ahead on one device: the messages the ring does not hold, hashed (raw) into reserved
+// slots, published once the launch has completed.  `sel` (optional): only messages j with sel[j]
+// != 0.  Chunks of at most the ring's size (and 1,024): a chunk's slots are published before the
+// next reserves, so a list longer than the ring leaves its LAST messages cached, as a FIFO should.
+int msg_ring_fill(BlsDev& d, size_t n, const uint8_t* base, const uint64_t* off, const uint32_t* len,
+                  const uint8_t* sel, const uint8_t* dst, size_t dl) {
+    if (!d.mr.on.load(std::memory_order_acquire) || dl > nwv::MsgKey::MAX_DST) return NWV_OK;
+    nwv::BlsMsgRing& R = d.mr.ring;
+    const size_t chunk = std::min<size_t>(R.cap(), 1024);
+    LaneLease lane(d);
+    if (lane.rc()) return lane.rc();
+    BlsLane& L = *lane;
+    int rc;
+    for (size_t j0 = 0; j0 < n;) {
+        MsgSlots ms;
+        ms.ring = &R;
+        ms.streams[0] = L.stream;
+        std::vector<uint32_t> aslot, alen;
+        std::vector<uint64_t> aoff;
+        std::vector<uint8_t> amsg;
+        size_t j = j0;
+        for (; j < n && aslot.size() < chunk; j++) {
+            if ((sel && !sel[j]) || len[j] > nwv::MsgKey::MAX_MSG) continue;
+            const nwv::MsgKey k = nwv::MsgKey::make(dst, dl, base + off[j], len[j]);
+            if (R.contains(k)) continue;
+            bool dup = false;
+            for (const MsgSlots::Fresh& f : ms.fresh) dup = dup || f.key == k;
+            if (dup) continue;
+            const uint32_t r = R.reserve();
+            if (r == nwv::BlsMsgRing::NONE) continue;  // every slot in use by calls in flight
+            ms.fresh.push_back({r, k, UINT32_MAX, true});
+            aslot.push_back(r);
+            alen.push_back(len[j]);
+            aoff.push_back(amsg.size());
+            amsg.insert(amsg.end(), base + off[j], base + off[j] + len[j]);
+        }
+        j0 = j;
+        const size_t m = aslot.size();
+        if (!m) continue;
+        const size_t o_slot = 8 * m, o_len = o_slot + 4 * m, o_dst = o_len + 4 * m, o_msg = o_dst + al256(dl + 1),
+                     total = o_msg + amsg.size() + 1;
+        if ((rc = L.stage.ensure(total)) || (rc = L.in.ensure(total))) return rc;
+        uint8_t* h = static_cast<uint8_t*>(L.stage.p);
+        uint8_t* in = static_cast<uint8_t*>(L.in.p);
+        std::memcpy(h, aoff.data(), 8 * m);
+        std::memcpy(h + o_slot, aslot.data(), 4 * m);
+        std::memcpy(h + o_len, alen.data(), 4 * m);
+        std::memcpy(h + o_dst, dst, dl);
+        if (!amsg.empty()) std::memcpy(h + o_msg, amsg.data(), amsg.size());
+        BLS_HIP(nwv_stage::stage_h2d(in, h, total, L.stream));
+        hipLaunchKernelGGL(k_blsw_h2c_ahead, dim3((unsigned)m), dim3(64), 0, L.stream, (uint32_t)m,
+                           (const uint8_t*)(in + o_msg), reinterpret_cast<const uint64_t*>(in),
+                           reinterpret_cast<const uint32_t*>(in + o_len), (const uint8_t*)(in + o_dst), (uint32_t)dl,
+                           static_cast<uint32_t*>(d.mr.rec.p), reinterpret_cast<const uint32_t*>(in + o_slot));
+        BLS_HIP(hipGetLastError());
+        BLS_HIP(hipStreamSynchronize(L.stream));
+        ms.finish(nullptr, nullptr);
+    }
+    return NWV_OK;
+}
+
 const uint8_t* dst_or_default(const uint8_t* dst, size_t* dl) {
     if (dst) return dst;
     *dl = sizeof(NWV_BLS_DST) - 1;
@@ -1923,12 +2182,19 @@ __attribute__((visibility("hidden"))) int nwv_bls_device_counters(nwv_ctx* ctx, 
     return 6;
 }
 
-extern "C" {
+// the message-ring counters of the calling thread's last verify call on a context (nwv_bls_last_msgs)
+struct MsgStat {
+    uint64_t v[5] = {0, 0, 0, 0, 0};
+};
+static thread_local std::unordered_map<const nwv_ctx*, MsgStat> t_last_msgs;
 
-int nwv_bls_verify_many(nwv_ctx* ctx, size_t n_keys, const uint8_t* keys, size_t n, const uint8_t* sigs,
-                        const uint32_t* pk_off, const uint32_t* pk_cnt, const uint32_t* pk_idx,
-                        const uint8_t* msg_base, const uint64_t* msg_off, const uint32_t* msg_len,
-                        const uint8_t* dst, size_t dst_len, int32_t* status) {
+// nwv_bls_verify_many, with the ahead messages of nwv_bls_verify_many_ahead (ah.n = 0: none)
+static int verify_many_impl(nwv_ctx* ctx, size_t n_keys, const uint8_t* keys, size_t n, const uint8_t* sigs,
+                            const uint32_t* pk_off, const uint32_t* pk_cnt, const uint32_t* pk_idx,
+                            const uint8_t* msg_base, const uint64_t* msg_off, const uint32_t* msg_len,
+                            const uint8_t* dst, size_t dst_len, int32_t* status, const Ahead& ah) {
+    MsgStat& mstat = t_last_msgs[ctx];
+    mstat = MsgStat{};
     if (n == 0) return NWV_OK;
     if (!sigs || !pk_off || !pk_cnt || !msg_off || !msg_len || !status || (n_keys && !keys))
         return nwv_internal_set_err(NWV_ERR_ARG, "null argument");
@@ -1959,8 +2225,9 @@ int nwv_bls_verify_many(nwv_ctx* ctx, size_t n_keys, const uint8_t* keys, size_t
     t_last_dev[ctx] = tickets[0].dev();
     if (ranges.size() == 1)
         return verify_on(*c->devs[tickets[0].dev()], n_keys, keys, n, sigs, pk_off, pk_cnt, pk_idx, n_idx, msg_base,
-                         msg_off, msg_len, msg_bytes, dst, dst_len, status);
+                         msg_off, msg_len, msg_bytes, dst, dst_len, status, ah.n ? &ah : nullptr, mstat.v);
     std::vector<std::string> err(ranges.size());
+    std::vector<MsgStat> rstat(ranges.size());  // (the ranges run on threads of their own)
     rc = bls_for_ranges(ranges, [&](size_t k, size_t lo, size_t hi) -> int {
         size_t ni = 0, mb = 0;  // the range's own key-index and message extents
         for (size_t i = lo; i < hi; i++) {
@@ -1969,14 +2236,121 @@ int nwv_bls_verify_many(nwv_ctx* ctx, size_t n_keys, const uint8_t* keys, size_t
         }
         const int e = verify_on(*c->devs[tickets[k].dev()], n_keys, keys, hi - lo, sigs + 48 * lo, pk_off + lo,
                                 pk_cnt + lo, pk_idx, ni, msg_base, msg_off + lo, msg_len + lo, mb, dst, dst_len,
-                                status + lo);
+                                status + lo, nullptr, rstat[k].v);
         if (e) err[k] = nwv_last_error();
         return e;
     });
     if (rc)  // the failing range's message, on the caller's thread
         for (size_t k = 0; k < err.size(); k++)
             if (!err[k].empty()) return nwv_internal_set_err(rc, err[k].c_str());
+    if (rc) return rc;
+    for (const MsgStat& s : rstat)
+        for (int k = 0; k < 5; k++) mstat.v[k] += s.v[k];
+    // a split call's ahead messages whose gates passed: hashed once the statuses are known, into
+    // every device's ring (a range cannot read another range's statuses)
+    if (ah.n) {
+        std::vector<uint8_t> sel(ah.n);
+        for (size_t j = 0; j < ah.n; j++)
+            sel[j] = !ah.gate || ah.gate[j] == UINT32_MAX || status[ah.gate[j]] == NWV_BLS_OK;
+        rc = on_all_devices(*c, [&](BlsDev& d) {
+            return msg_ring_fill(d, ah.n, ah.base, ah.off, ah.len, sel.data(), dst, dst_len);
+        });
+    }
     return rc;
+}
+
+extern "C" {
+
+int nwv_bls_verify_many(nwv_ctx* ctx, size_t n_keys, const uint8_t* keys, size_t n, const uint8_t* sigs,
+                        const uint32_t* pk_off, const uint32_t* pk_cnt, const uint32_t* pk_idx,
+                        const uint8_t* msg_base, const uint64_t* msg_off, const uint32_t* msg_len,
+                        const uint8_t* dst, size_t dst_len, int32_t* status) {
+    return verify_many_impl(ctx, n_keys, keys, n, sigs, pk_off, pk_cnt, pk_idx, msg_base, msg_off, msg_len, dst,
+                            dst_len, status, Ahead{});
+}
+
+int nwv_bls_verify_many_ahead(nwv_ctx* ctx, size_t n_keys, const uint8_t* keys, size_t n, const uint8_t* sigs,
+                              const uint32_t* pk_off, const uint32_t* pk_cnt, const uint32_t* pk_idx,
+                              const uint8_t* msg_base, const uint64_t* msg_off, const uint32_t* msg_len,
+                              const uint8_t* dst, size_t dst_len, int32_t* status, size_t n_ahead,
+                              const uint8_t* ahead_base, const uint64_t* ahead_off, const uint32_t* ahead_len,
+                              const uint32_t* ahead_gate) {
+    Ahead ah;
+    if (n_ahead) {
+        if (!ahead_off || !ahead_len) return nwv_internal_set_err(NWV_ERR_ARG, "null argument");
+        if (n_ahead > (1u << 20)) return nwv_internal_set_err(NWV_ERR_ARG, "too many ahead messages");
+        for (size_t j = 0; j < n_ahead; j++) {
+            if (ahead_len[j] && !ahead_base) return nwv_internal_set_err(NWV_ERR_ARG, "null ahead_base");
+            if (ahead_gate && ahead_gate[j] != UINT32_MAX && ahead_gate[j] >= n)
+                return nwv_internal_set_err(NWV_ERR_ARG, "ahead gate out of range");
+        }
+        ah = Ahead{n_ahead, ahead_base, ahead_off, ahead_len, ahead_gate};
+    }
+    return verify_many_impl(ctx, n_keys, keys, n, sigs, pk_off, pk_cnt, pk_idx, msg_base, msg_off, msg_len, dst,
+                            dst_len, status, ah);
+}
+
+int nwv_bls_set_msg_ring(nwv_ctx* ctx, size_t slots) {
+    BlsCtx* c;
+    int rc = ctx_of(ctx, &c);
+    if (rc) return rc;
+    if (slots > nwv::BlsMsgRing::MAX_SLOTS) return nwv_internal_set_err(NWV_ERR_ARG, "message ring larger than 65,536 slots");
+    static std::mutex mu;  // one setter at a time
+    std::lock_guard<std::mutex> g(mu);
+    if (slots) {
+        for (BlsDev* d : c->devs)
+            if (d->mr.ring.cap() && d->mr.ring.cap() != slots)
+                return nwv_internal_set_err(NWV_ERR_ARG, "the message ring's size is fixed once set");
+        for (BlsDev* d : c->devs) {
+            if (d->mr.ring.cap()) continue;
+            if (hipSetDevice(d->ordinal) != hipSuccess) return nwv_internal_set_err(NWV_ERR_HIP, "hipSetDevice (bls)");
+            if ((rc = d->mr.rec.ensure((size_t)4 * G1H_REC_WORDS * slots))) return rc;
+            d->mr.ring.init((uint32_t)slots);
+        }
+    }
+    for (BlsDev* d : c->devs) d->mr.on.store(slots != 0, std::memory_order_release);
+    return NWV_OK;
+}
+
+size_t nwv_bls_msg_ring(const nwv_ctx* ctx) {
+    BlsCtx* c;
+    if (ctx_of(const_cast<nwv_ctx*>(ctx), &c)) return 0;
+    BlsDev* d = c->devs[0];
+    return d->mr.on.load(std::memory_order_acquire) ? d->mr.ring.cap() : 0;
+}
+
+int nwv_bls_hash_ahead(nwv_ctx* ctx, size_t n, const uint8_t* msg_base, const uint64_t* msg_off,
+                       const uint32_t* msg_len, const uint8_t* dst, size_t dst_len) {
+    if (n == 0) return NWV_OK;
+    if (!msg_off || !msg_len) return nwv_internal_set_err(NWV_ERR_ARG, "null argument");
+    for (size_t j = 0; j < n; j++)
+        if (msg_len[j] && !msg_base) return nwv_internal_set_err(NWV_ERR_ARG, "null msg_base");
+    dst = dst_or_default(dst, &dst_len);
+    if (dst_len > 255) return nwv_internal_set_err(NWV_ERR_ARG, "DST longer than 255 bytes");
+    BlsCtx* c;
+    int rc = ctx_of(ctx, &c);
+    if (rc) return rc;
+    // every device: placement may send the later call to any of them
+    return on_all_devices(*c, [&](BlsDev& d) { return msg_ring_fill(d, n, msg_base, msg_off, msg_len, nullptr, dst, dst_len); });
+}
+
+int nwv_bls_last_msgs(nwv_ctx* ctx, uint64_t out[5]) {
+    if (!out) return nwv_internal_set_err(NWV_ERR_ARG, "null argument");
+    BlsCtx* c;
+    int rc = ctx_of(ctx, &c);
+    if (rc) return rc;
+    const auto it = t_last_msgs.find(ctx);
+    for (int k = 0; k < 5; k++) out[k] = it != t_last_msgs.end() ? it->second.v[k] : 0;
+    return NWV_OK;
+}
+
+int nwv_bls_msg_ring_stats(nwv_ctx* ctx, uint64_t out[3]) {
+    if (!out) return nwv_internal_set_err(NWV_ERR_ARG, "null argument");
+    BlsDev* d;
+    int rc = last_dev_of(ctx, &d);
+    if (rc) return rc;
+    d->mr.ring.counts(out);
+    return NWV_OK;
 }
 
 int nwv_bls_last_kernel_ms(nwv_ctx* ctx, double out_ms[5]) {

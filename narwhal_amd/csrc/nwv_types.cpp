@@ -622,13 +622,24 @@ struct BlsItems {
         put(msg, m, 32);
         return (long)off.size() - 1;
     }
-    int run(nwv_ctx* ctx, const nwv_bls_committee& c) {
+    // ahead: 32-byte messages to hash into the device's message ring beside the checks, message j
+    // kept only if item gate[j] verifies (nwv_bls_verify_many_ahead)
+    int run(nwv_ctx* ctx, const nwv_bls_committee& c, const std::vector<uint8_t>* ahead = nullptr,
+            const std::vector<uint32_t>* gate = nullptr) {
         st.assign(off.size(), 0);
         if (off.empty()) return NWV_OK;
         msg.resize(msg.size() + 8);
-        return nwv_bls_verify_many(ctx, c.n, c.keys, off.size(), sig.data(), off.data(), cnt.data(),
-                                   idx.empty() ? nullptr : idx.data(), msg.data(), moff.data(), mlen.data(), nullptr, 0,
-                                   st.data());
+        if (!ahead || gate->empty())
+            return nwv_bls_verify_many(ctx, c.n, c.keys, off.size(), sig.data(), off.data(), cnt.data(),
+                                       idx.empty() ? nullptr : idx.data(), msg.data(), moff.data(), mlen.data(),
+                                       nullptr, 0, st.data());
+        std::vector<uint64_t> aoff(gate->size());
+        const std::vector<uint32_t> alen(gate->size(), 32);
+        for (size_t j = 0; j < aoff.size(); j++) aoff[j] = 32 * j;
+        return nwv_bls_verify_many_ahead(ctx, c.n, c.keys, off.size(), sig.data(), off.data(), cnt.data(),
+                                         idx.empty() ? nullptr : idx.data(), msg.data(), moff.data(), mlen.data(),
+                                         nullptr, 0, st.data(), gate->size(), ahead->data(), aoff.data(), alen.data(),
+                                         gate->data());
     }
 };
 
@@ -660,6 +671,18 @@ int bls_verify_mixed(nwv_ctx* ctx, const nwv_bls_committee& c, size_t nh, const 
         bls_plan_header(c, x.header, db, cplan[i]);
         cdig[i] = (long)db.add_begin();
         bls_id_round_epoch_origin(x.header.id, x.header.round, x.header.epoch, x.header.author, db.arena);
+        db.add_end();
+    }
+    // With the context's message ring on (nwv_bls_set_msg_ring): the digest of the certificate
+    // each header will get, id || round || epoch || author, in the same launch.  The votes for the
+    // header and its certificate all sign that digest, and they arrive a round trip later: its
+    // H(m) is hashed beside this call's checks and kept if the header's signature verifies.
+    const bool ring = nh && nwv_bls_msg_ring(ctx) != 0;
+    std::vector<long> adig(nh, -1);
+    for (size_t i = 0; ring && i < nh; i++) {
+        if (hplan[i].pre || hplan[i].post) continue;
+        adig[i] = (long)db.add_begin();
+        bls_id_round_epoch_origin(h[i].id, h[i].round, h[i].epoch, h[i].author, db.arena);
         db.add_end();
     }
     // phase 2: the digests (one BLAKE2b launch), then every signature check (one BLS call)
@@ -708,7 +731,14 @@ int bls_verify_mixed(nwv_ctx* ctx, const nwv_bls_committee& c, size_t nh, const 
         asig[i] = items.add(x.aggregated_signature, pks.data(), pks.size(), dig.data() + 32 * cdig[i]);
     }
     if ((rc = nwv_bls_keycache_register(ctx, c.n, c.keys))) return rc;  // no-op once registered
-    if ((rc = items.run(ctx, c))) return rc;
+    std::vector<uint8_t> ahead;
+    std::vector<uint32_t> gate;
+    for (size_t i = 0; ring && i < nh; i++)
+        if (hsig[i] >= 0 && adig[i] >= 0) {
+            put(ahead, dig.data() + 32 * adig[i], 32);
+            gate.push_back((uint32_t)hsig[i]);
+        }
+    if ((rc = items.run(ctx, c, ring ? &ahead : nullptr, &gate))) return rc;
     auto bad = [&](long k) { return k >= 0 && items.st[k] != NWV_BLS_OK; };
     // phase 3: verdicts in the reference's check order
     for (size_t i = 0; i < nh; i++) {

@@ -373,3 +373,38 @@ pub fn verify_many(
         Err(last_error())
     }
 }
+
+/// Turn the engine's message ring on with `slots` records per device (once, at start-up; 0
+/// switches it off again): the hash to G1 of a message that recurs -- the votes for a header and
+/// its certificate sign one digest -- is then computed once and kept.
+pub fn msg_ring_enable(slots: usize) -> Result<(), String> {
+    let rc = unsafe { ffi::nwv_bls_set_msg_ring(ctx(), slots) };
+    if rc == ffi::NWV_OK {
+        Ok(())
+    } else {
+        Err(last_error())
+    }
+}
+
+/// Hash messages into the ring ahead of the calls that verify over them.  The Proposer calls this
+/// with the certificate digest of the header it has just made: that header never passes
+/// `sanitize_header`, and its votes and certificate are the hits.  A no-op with the ring off.
+pub fn hash_ahead(msgs: &[&[u8]]) -> Result<(), String> {
+    let mut mb: Vec<u8> = Vec::new();
+    let mut moff = Vec::with_capacity(msgs.len());
+    let mut mlen = Vec::with_capacity(msgs.len());
+    for m in msgs {
+        moff.push(mb.len() as u64);
+        mlen.push(m.len() as u32);
+        mb.extend_from_slice(m);
+    }
+    mb.push(0);
+    let rc = unsafe {
+        ffi::nwv_bls_hash_ahead(ctx(), msgs.len(), mb.as_ptr(), moff.as_ptr(), mlen.as_ptr(), std::ptr::null(), 0)
+    };
+    if rc == ffi::NWV_OK {
+        Ok(())
+    } else {
+        Err(last_error())
+    }
+}

@@ -337,6 +337,40 @@ extern "C" {
     pub fn nwv_bls_wave_batch_min(ctx: *const NwvCtx) -> usize;
     pub fn nwv_bls_last_batch(ctx: *mut NwvCtx, out: *mut u64) -> c_int;
     pub fn nwv_bls_last_keys(ctx: *mut NwvCtx, out: *mut u64) -> c_int;
+    pub fn nwv_bls_set_msg_ring(ctx: *mut NwvCtx, slots: usize) -> c_int;
+    pub fn nwv_bls_msg_ring(ctx: *const NwvCtx) -> usize;
+    pub fn nwv_bls_hash_ahead(
+        ctx: *mut NwvCtx,
+        n: usize,
+        msg_base: *const u8,
+        msg_off: *const u64,
+        msg_len: *const u32,
+        dst: *const u8,
+        dst_len: usize,
+    ) -> c_int;
+    pub fn nwv_bls_verify_many_ahead(
+        ctx: *mut NwvCtx,
+        n_keys: usize,
+        keys: *const u8,
+        n: usize,
+        sigs: *const u8,
+        pk_off: *const u32,
+        pk_cnt: *const u32,
+        pk_idx: *const u32,
+        msg_base: *const u8,
+        msg_off: *const u64,
+        msg_len: *const u32,
+        dst: *const u8,
+        dst_len: usize,
+        status: *mut i32,
+        n_ahead: usize,
+        ahead_base: *const u8,
+        ahead_off: *const u64,
+        ahead_len: *const u32,
+        ahead_gate: *const u32,
+    ) -> c_int;
+    pub fn nwv_bls_last_msgs(ctx: *mut NwvCtx, out: *mut u64) -> c_int;
+    pub fn nwv_bls_msg_ring_stats(ctx: *mut NwvCtx, out: *mut u64) -> c_int;
     pub fn nwv_bls_keycache_register(ctx: *mut NwvCtx, n_keys: usize, keys: *const u8) -> c_int;
     pub fn nwv_bls_keycache_reset(ctx: *mut NwvCtx) -> c_int;
     pub fn nwv_bls_keycache_size(ctx: *mut NwvCtx) -> c_int;

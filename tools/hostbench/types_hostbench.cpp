@@ -44,6 +44,15 @@ extern "C" int nwv_bls_verify_many(nwv_ctx*, size_t, const uint8_t*, size_t n, c
     std::memset(status, 0, 4 * n);
     return NWV_OK;
 }
+// (the message ring is off in the stubbed engine: the types layer then never calls the ahead form)
+extern "C" size_t nwv_bls_msg_ring(const nwv_ctx*) { return 0; }
+extern "C" int nwv_bls_verify_many_ahead(nwv_ctx*, size_t, const uint8_t*, size_t n, const uint8_t*, const uint32_t*,
+                                         const uint32_t*, const uint32_t*, const uint8_t*, const uint64_t*,
+                                         const uint32_t*, const uint8_t*, size_t, int32_t* status, size_t,
+                                         const uint8_t*, const uint64_t*, const uint32_t*, const uint32_t*) {
+    std::memset(status, 0, 4 * n);
+    return NWV_OK;
+}
 extern "C" int nwv_bls_aggregate(nwv_ctx*, size_t, const uint8_t*, uint8_t out48[48], int32_t*) {
     std::memset(out48, 0, 48);
     return NWV_OK;
