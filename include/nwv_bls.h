@@ -133,6 +133,33 @@ int nwv_bls_last_msgs(nwv_ctx* ctx, uint64_t out[5]);
  * pinned (read by a call in flight) */
 int nwv_bls_msg_ring_stats(nwv_ctx* ctx, uint64_t out[3]);
 
+/* The aggregate-key ring (per device): the key side of a recurring signer set.  A certificate's
+ * item sums its signers' keys and computes that sum's Miller-loop lines step by step, where a
+ * registered key's item reads a table made at registration; a small committee has few quorums and
+ * certificates are validated and fetched again, so the ring keeps, per set, the affine sum of the
+ * signers' [h_eff] pk records and its line table, and an item whose set is held runs as a one-key
+ * item by a registered key.  Opt-in: slots = 0 (the default) means no lookups and no publishes, and
+ * every call takes exactly the launches it takes without this setting.  The first non-zero value
+ * allocates `slots` records (about 23 KB each, at most 4,096) on every BLS device object; a later
+ * different non-zero value is NWV_ERR_ARG (the buffers never move); a later 0 switches lookups and
+ * publishes off.  Only calls on the small wave path use the ring (at most NWV_BLS_WAVE_MAX and at
+ * most 1,024 items, neither NWV_FLAG_BLS_BATCH nor NWV_FLAG_BLS_PER_ITEM), and only items of 2 to
+ * 1,024 keys that are all in the key cache; a set is the sorted list of its keys' cache slots,
+ * duplicates kept.  A set is filled at its second sighting (a table of 4 x slots set hashes
+ * remembers the first), by the call that sees it, beside that call's pairing check, and kept only
+ * if the item verified: a forged aggregate, an identity sum or any other failure publishes
+ * nothing.  nwv_bls_keycache_reset empties the ring.  Statuses never depend on the ring. */
+int nwv_bls_set_apk_ring(nwv_ctx* ctx, size_t slots);
+size_t nwv_bls_apk_ring(const nwv_ctx* ctx);
+/* the ring's part in the calling thread's last verify call on this context: out[0] items served
+ * from the ring, out[1] items eligible and not found, out[2] of those, sets noted as seen once,
+ * out[3] sets this call published.  All zero when the call did not use the ring. */
+int nwv_bls_last_apk(nwv_ctx* ctx, uint64_t out[4]);
+/* slot counts of the ring of the device that served the calling thread's last verify call:
+ * out[0] held (published under a set), out[1] busy (reserved by a call in flight), out[2] pinned
+ * (read by a call in flight) */
+int nwv_bls_apk_ring_stats(nwv_ctx* ctx, uint64_t out[3]);
+
 /* The committee key cache (per device).  fastcrypto decodes and validates a public key once, at
  * deserialization; nwv_bls_keycache_register does that once per device for the committee's keys
  * (epoch start, Core::change_epoch primary/src/core.rs:592-611) and keeps the records of the keys

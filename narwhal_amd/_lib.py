@@ -114,6 +114,19 @@ def load():
         f = getattr(lib, name)
         f.argtypes = args
         f.restype = res
+    # the aggregate-key ring's entry points (narwhal_amd.bls wraps them); an older build selected
+    # with NWV_LIB for an A/B run lacks them, and calling one there still raises
+    newer = {
+        "nwv_bls_set_apk_ring": ([_vp, _sz], _i32),
+        "nwv_bls_apk_ring": ([_vp], _sz),
+        "nwv_bls_last_apk": ([_vp, _vp], _i32),
+        "nwv_bls_apk_ring_stats": ([_vp, _vp], _i32),
+    }
+    for name, (args, res) in newer.items():
+        f = getattr(lib, name, None)
+        if f is not None:
+            f.argtypes = args
+            f.restype = res
     _lib = lib
     return lib
 

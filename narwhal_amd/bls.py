@@ -38,7 +38,12 @@ _SIGS = {
                                    _sz, _vp, _vp, _vp, _vp], _i32),
     "nwv_bls_last_msgs": ([_vp, _vp], _i32),
     "nwv_bls_msg_ring_stats": ([_vp, _vp], _i32),
+    "nwv_bls_set_apk_ring": ([_vp, _sz], _i32),
+    "nwv_bls_apk_ring": ([_vp], _sz),
+    "nwv_bls_last_apk": ([_vp, _vp], _i32),
+    "nwv_bls_apk_ring_stats": ([_vp, _vp], _i32),
 }
+APK_COUNTERS = ("hits", "missed", "noted", "published")
 MSG_COUNTERS = ("hits_copied", "hits_chained", "computed", "published", "ahead_published")
 NO_GATE = 0xFFFFFFFF
 KERNELS = ("keys_new_to_cache", "sig_decode", "hash_to_g1", "key_sums", "pairing_check")
@@ -149,6 +154,25 @@ class Bls:
         """(held, busy, pinned) slots of the ring that served this thread's last verify call"""
         out = np.zeros(3, dtype=np.uint64)
         _lib._check(self.lib.nwv_bls_msg_ring_stats(self._h, out.ctypes.data))
+        return int(out[0]), int(out[1]), int(out[2])
+
+    # the aggregate-key ring (recurring signer sets' key sums and line tables per device): off at 0
+    def set_apk_ring(self, slots):
+        _lib._check(self.lib.nwv_bls_set_apk_ring(self._h, slots))
+
+    def apk_ring(self):
+        return int(self.lib.nwv_bls_apk_ring(self._h))
+
+    def last_apk(self):
+        """{counter: count} of the ring's part in this thread's last verify call (APK_COUNTERS)"""
+        out = np.zeros(4, dtype=np.uint64)
+        _lib._check(self.lib.nwv_bls_last_apk(self._h, out.ctypes.data))
+        return dict(zip(APK_COUNTERS, (int(x) for x in out)))
+
+    def apk_ring_stats(self):
+        """(held, busy, pinned) slots of the ring that served this thread's last verify call"""
+        out = np.zeros(3, dtype=np.uint64)
+        _lib._check(self.lib.nwv_bls_apk_ring_stats(self._h, out.ctypes.data))
         return int(out[0]), int(out[1]), int(out[2])
 
     def verify_many_arrays(self, keys, sigs, pk_off, pk_cnt, pk_idx, arena, offs, lens, status, dst=None):

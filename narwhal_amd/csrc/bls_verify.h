@@ -259,15 +259,10 @@ G_HD bool g_rlc_final(const GCtx& g, const uint32_t* f_rec) { return g_is_one(g,
 // ---- the same check on one whole wave (bls_wave.h) -------------------------------------------
 // the line table of an affine Q (a G2 record): (l0, l1, l4) of every Miller-loop step, NSTEPS x 6
 // slots of 14 words -- what the loop computes from T when no table is given
+// (the steps alone: QB holds Q with Z = 1)
 template <class W>
-NWV_HD void w_key_lines(const W& w, const uint32_t* q_rec, uint32_t* out) {
+NWV_HD void w_key_lines_steps(const W& w, uint32_t* out) {
     using namespace wave;
-    init_slots(w);
-    w.zero(REG_QB, 6);
-    w.sync();
-    w.put_words(REG_QB, q_rec, 4);
-    w.put_fp(REG_QB + 4, k_one());
-    w.sync();
     w.put_words(REG_TB, w.wm + SW * REG_QB, 6);
     w.sync();
     const char* steps = BLS_WAVE_STEPS_STR;
@@ -277,6 +272,49 @@ NWV_HD void w_key_lines(const W& w, const uint32_t* q_rec, uint32_t* out) {
         w.get_words(REG_LB, out + (size_t)k * 6 * SW, 6);
         w.sync();
     }
+}
+template <class W>
+NWV_HD void w_key_lines(const W& w, const uint32_t* q_rec, uint32_t* out) {
+    using namespace wave;
+    init_slots(w);
+    w.zero(REG_QB, 6);
+    w.sync();
+    w.put_words(REG_QB, q_rec, 4);
+    w.put_fp(REG_QB + 4, k_one());
+    w.sync();
+    w_key_lines_steps(w, out);
+}
+// The fill of an aggregate-key ring slot (bls_apk_ring.h) on a wave: a key-side item's Jacobian
+// key sum (blsw_apk_item's record: the sum of its keys' [h_eff] pk records) made affine with one
+// Fp2 inversion -- every lane forms the norm, the wave inverts it -- written to `rec` as a G2
+// record with canonical limbs (one sum, one record, by whichever route it was added up), and that
+// point's line table to `lines`: what registration keeps for one key (k_bls_key_heff,
+// k_blsw_key_lines), for the set.  st: the item's key status; a sum that is not OK (a bad key, the
+// identity) is not handed on: nothing is written and false comes back.
+template <class W>
+NWV_HD bool w_apk_fill(const W& w, const uint32_t* aj, int32_t st, uint32_t* rec, uint32_t* lines) {
+    using namespace wave;
+    if (st != ST_OK || aj[6 * NL] != 0) return false;
+    const fp2 X = ld_f2(aj), Y = ld_f2(aj + 2 * NL), Z = ld_f2(aj + 4 * NL);
+    const fp n = w.inv(fp_add(fp_sqr(Z.c0), fp_sqr(Z.c1)));
+    const fp2 zi = {fp_mul(Z.c0, n), fp_neg(fp_mul(Z.c1, n))}, zi2 = f2_sqr(zi);
+    fp2 x = f2_mul(X, zi2), y = f2_mul(Y, f2_mul(zi2, zi));
+    x.c0 = fp_canon(x.c0);
+    x.c1 = fp_canon(x.c1);
+    y.c0 = fp_canon(y.c0);
+    y.c1 = fp_canon(y.c1);
+    w.lanes(1, [&](int) { st_g2(rec, x, y, false); });
+    init_slots(w);
+    w.zero(REG_QB, 6);
+    w.sync();
+    w.put_fp(REG_QB, x.c0);
+    w.put_fp(REG_QB + 1, x.c1);
+    w.put_fp(REG_QB + 2, y.c0);
+    w.put_fp(REG_QB + 3, y.c1);
+    w.put_fp(REG_QB + 4, k_one());
+    w.sync();
+    w_key_lines_steps(w, lines);
+    return true;
 }
 
 // e(-sig, g2) e(H, apk) == 1 from the item's records (sig, H affine G1 records, apk an affine G2

@@ -37,6 +37,7 @@
 #include "bls_verify.h"
 #include "bls_shard.h"
 #include "bls_msg_ring.h"
+#include "bls_apk_ring.h"
 #include "place.h"
 #include "stage_args.h"
 
@@ -74,9 +75,15 @@ __global__ __launch_bounds__(BLS_LANES) void k_bls_rec_copy(uint32_t n, const ui
     to[(size_t)G2_REC_WORDS * dst[i] + w] = from[(size_t)G2_REC_WORDS * src[i] + w];
     if (w == 0) to_st[dst[i]] = ST_OK;
 }
-// A call's key table: index k < KC_CAP names slot k of the device's key cache, k >= KC_CAP entry
-// k - KC_CAP of the call's scratch table (keys the cache does not hold, decoded by this call)
+// A call's key table: index k < KC_CAP names slot k of the device's key cache, KC_CAP <= k < AR_BASE
+// entry k - KC_CAP of the call's scratch table (keys the cache does not hold, decoded by this
+// call: up to MAX_CALL_KEYS of them, far more than the cache has slots), k >= AR_BASE slot
+// k - AR_BASE of the device's aggregate-key ring (a recurring signer set's key sum standing in as
+// the one key of its item: always valid, an [h_eff]-side record with a line table of its own)
 constexpr uint32_t KC_CAP = 65536;
+constexpr uint32_t MAX_CALL_KEYS = 1u << 26;  // nwv_bls_verify_many's limit on n_keys (and on n)
+constexpr uint32_t AR_BASE = 0x80000000u;
+static_assert(KC_CAP + MAX_CALL_KEYS <= AR_BASE, "no scratch index reaches the ring's range");
 constexpr uint32_t SC_CAP = 65536;  // the verified-signature ring (BlsSigCache)
 struct KeyTab {
     const uint32_t* rc;
@@ -85,13 +92,23 @@ struct KeyTab {
     const int32_t* ss;
     const uint32_t* lines;  // cached keys' Miller-loop line tables (KL_WORDS per slot), or null
     const uint32_t* hrc;    // cached keys' [h_eff] pk records (G2_REC_WORDS per slot), or null
+    const uint32_t* arr;    // the aggregate-key ring's records (G2_REC_WORDS per slot), or null
+    const uint32_t* arl;    // the ring's line tables (KL_WORDS per slot), or null
 };
 // words of a registered key's line table: (l0, l1, l4) of every Miller-loop step (w_key_lines)
 constexpr size_t KL_WORDS = (size_t)wave::NSTEPS * 6 * wave::SW;
 __device__ inline const uint32_t* key_rec(const KeyTab& t, uint32_t k) {
-    return k < KC_CAP ? t.rc + (size_t)G2_REC_WORDS * k : t.rs + (size_t)G2_REC_WORDS * (k - KC_CAP);
+    return k < KC_CAP    ? t.rc + (size_t)G2_REC_WORDS * k
+           : k < AR_BASE ? t.rs + (size_t)G2_REC_WORDS * (k - KC_CAP)
+                         : t.arr + (size_t)G2_REC_WORDS * (k - AR_BASE);
 }
-__device__ inline int32_t key_st(const KeyTab& t, uint32_t k) { return k < KC_CAP ? t.sc[k] : t.ss[k - KC_CAP]; }
+__device__ inline int32_t key_st(const KeyTab& t, uint32_t k) {
+    return k < KC_CAP ? t.sc[k] : k < AR_BASE ? t.ss[k - KC_CAP] : ST_OK;
+}
+// the line table of a one-key, key-side item's key: a cache slot's or a ring slot's
+__device__ inline const uint32_t* key_lines(const KeyTab& t, uint32_t k) {
+    return k < AR_BASE ? t.lines + KL_WORDS * k : t.arl + KL_WORDS * (k - AR_BASE);
+}
 __global__ __launch_bounds__(BLS_LANES) void k_bls_sigs(uint32_t n, const uint8_t* sig, uint32_t* rec, int32_t* st) {
     BLS_IDX();
     st[i] = sig_decode(sig + 48 * (size_t)i, rec + (size_t)G1_REC_WORDS * i);
@@ -416,7 +433,7 @@ __device__ __forceinline__ void blsw_pair_item(uint32_t* wm, uint32_t i, const u
     int32_t s = ST_VERIFY_FAIL;
     if (st_dec[i] == ST_OK && st_apk[i] == ST_OK) {
         const uint32_t* ql = nullptr;
-        if (kt.lines && kmode && kmode[i] && pk_cnt[i] == 1) ql = kt.lines + KL_WORDS * pk_idx[pk_off[i]];
+        if (kt.lines && kmode && kmode[i] && pk_cnt[i] == 1) ql = key_lines(kt, pk_idx[pk_off[i]]);
         s = w_pairing_check_g(w, srec + (size_t)G1_REC_WORDS * i,
                               hrec + (size_t)(h_hom ? G1H_REC_WORDS : G1_REC_WORDS) * i, h_hom != 0,
                               arec + (size_t)G2J_WORDS * i, true, ql)
@@ -502,7 +519,7 @@ __device__ __forceinline__ void pair_flat(uint32_t* lds_k, uint32_t i0, int k, c
         }
         sig[j] = MILLER ? nullptr : srec + (size_t)G1_REC_WORDS * i;
         hr[j] = hrec + (size_t)(h_hom ? G1H_REC_WORDS : G1_REC_WORDS) * i;
-        ql[j] = (kt.lines && kmode && kmode[i] && pk_cnt[i] == 1) ? kt.lines + KL_WORDS * pk_idx[pk_off[i]] : nullptr;
+        ql[j] = (kt.lines && kmode && kmode[i] && pk_cnt[i] == 1) ? key_lines(kt, pk_idx[pk_off[i]]) : nullptr;
         fixed = fixed && ql[j] != nullptr;
     }
     // P << k once, then every bank: slot 0 = 0, the pairing check's constants at slots 1..
@@ -828,6 +845,20 @@ __global__ __launch_bounds__(64) void k_blsw_key_lines(uint32_t n, const uint32_
     const wave::Wave w{wm, (int)threadIdx.x};
     w_key_lines(w, rc + (size_t)G2_REC_WORDS * k, lines + KL_WORDS * k);
 }
+// the fills of a call's aggregate-key ring slots (bls_apk_ring.h), one wave per set: item item[j]'s
+// Jacobian key sum (k_blsw_pre's arec) made affine into record slot[j] of the ring, and that
+// point's line table (w_apk_fill).  A sum whose status is not OK writes nothing (the host never
+// publishes its slot).  The host keeps the slots away from every other call until this one has
+// synchronised (busy flags).
+__global__ __launch_bounds__(64) void k_blsw_apk_fill(uint32_t n, const uint32_t* item, const uint32_t* slot,
+                                                      const uint32_t* arec, const int32_t* st_apk, uint32_t* ring_rec,
+                                                      uint32_t* ring_lines) {
+    BLSW_IDX();
+    const wave::Wave w{wm, (int)threadIdx.x};
+    const uint32_t it = item[i], k = slot[i];
+    w_apk_fill(w, arec + (size_t)G2J_WORDS * it, st_apk[it], ring_rec + (size_t)G2_REC_WORDS * k,
+               ring_lines + KL_WORDS * k);
+}
 // the key sum of item i on a wave: lane j adds the item's keys j, j + 64, ... (Jacobian, jac_add:
 // exact in every case), then a six-level tree through LDS.  The status is that of the item's first
 // bad key in list order (else AGGR_MISMATCH for an empty list, PK_INFINITY for an identity sum).
@@ -1125,8 +1156,9 @@ struct BlsLane {
     // [11] side 1 done.  side[1] is created by the first call that needs it: a lane of small wave
     // calls holds two streams, so eight lanes map one to one onto 16 hardware queues
     hipEvent_t ev[12] = {};
-    // ordering only (no timestamps): [0] inputs resident, [1] signatures decoded (small wave calls)
-    hipEvent_t sev[2] = {};
+    // ordering only (no timestamps): [0] inputs resident, [1] signatures decoded (small wave calls),
+    // [2] key sums done (small wave calls that fill aggregate-key ring slots)
+    hipEvent_t sev[3] = {};
     ~BlsLane() {
         for (auto& e : ev)
             if (e) (void)hipEventDestroy(e);
@@ -1277,6 +1309,51 @@ struct MsgSlots {
         for (uint32_t s : pinned) ring->unpin(s);
     }
 };
+// The aggregate keys of a device (nwv_bls_set_apk_ring; bls_apk_ring.h keeps the books): per slot
+// the affine sum of a signer set's [h_eff] pk records and that point's line table.  A small wave
+// call looks the sets of its key-side items up and pins the hits, whose items then run as one-key
+// items on the slot; a set missed for the second time reserves a slot, k_blsw_apk_fill writes it
+// beside the pairing kernel, and the call publishes it after its streams have synchronised if the
+// item verified.  The sets are lists of key-cache slots: nwv_bls_keycache_reset empties the ring.
+struct BlsApkCache {
+    nwv::BlsApkRing ring;
+    DBuf rec;                     // ring.cap() x G2_REC_WORDS u32
+    DBuf lines;                   // ring.cap() x KL_WORDS u32
+    std::atomic<bool> on{false};  // lookups and publishes (the buffers, once there, stay)
+};
+// a call's aggregate-key slots: the hits it pinned and the slots it reserved.  finish() publishes
+// (behind each item's status) and unpins after the call's streams have synchronised; a call that
+// fails before that synchronises them here and gives everything back, and if that wait fails too
+// the slots stay pinned / busy (abandoned, as MsgSlots does).
+struct ApkSlots {
+    struct Fresh {
+        uint32_t slot, item;
+        nwv::ApkKey key;
+    };
+    nwv::BlsApkRing* ring = nullptr;
+    std::vector<uint32_t> pinned;
+    std::vector<Fresh> fresh;
+    hipStream_t streams[2] = {nullptr, nullptr};
+    // a set is kept only if the item that reserved its slot verified: out[3] += published slots
+    void finish(const int32_t* status, uint64_t* out) {
+        if (!ring) return;
+        for (const Fresh& f : fresh) {
+            if (status[f.item] != ST_OK)
+                ring->release(f.slot);
+            else if (ring->publish(f.slot, f.key) == f.slot)
+                out[3]++;
+        }
+        for (uint32_t s : pinned) ring->unpin(s);
+        ring = nullptr;
+    }
+    ~ApkSlots() {
+        if (!ring) return;
+        for (hipStream_t s : streams)
+            if (s && hipStreamSynchronize(s) != hipSuccess) return;  // abandoned, see above
+        for (const Fresh& f : fresh) ring->release(f.slot);
+        for (uint32_t s : pinned) ring->unpin(s);
+    }
+};
 // a call's ahead messages (nwv_bls_verify_many_ahead)
 struct Ahead {
     size_t n = 0;
@@ -1292,6 +1369,7 @@ struct BlsDev {
     BlsKeyCache kc;
     BlsSigCache sc;
     BlsMsgCache mr;
+    BlsApkCache ar;
     std::mutex pool_mu;
     std::condition_variable pool_cv;
     std::vector<std::unique_ptr<BlsLane>> lanes;
@@ -1570,7 +1648,7 @@ int keycache_register(BlsDev& d, size_t n_keys, const uint8_t* keys) {
 int verify_on(BlsDev& d, size_t n_keys, const uint8_t* keys, size_t n, const uint8_t* sigs, const uint32_t* pk_off,
               const uint32_t* pk_cnt, const uint32_t* pk_idx, size_t n_idx, const uint8_t* msg_base,
               const uint64_t* msg_off, const uint32_t* msg_len, size_t msg_bytes, const uint8_t* dst, size_t dl,
-              int32_t* status, const Ahead* ahead = nullptr, uint64_t* mstat = nullptr) {
+              int32_t* status, const Ahead* ahead = nullptr, uint64_t* mstat = nullptr, uint64_t* astat = nullptr) {
     LaneLease lane(d);
     if (lane.rc()) return lane.rc();
     BlsLane& L = *lane;
@@ -1723,19 +1801,73 @@ int verify_on(BlsDev& d, size_t n_keys, const uint8_t* keys, size_t n, const uin
         std::memcpy(rsec.data() + r_hsrc, hsrc.data(), 4 * n);
         std::memcpy(rsec.data() + r_hpub, hpub.data(), 4 * n);
     }
+    // the device's aggregate-key ring (the same small wave calls): the key-side items of 2 to 1,024
+    // keys.  A hit is pinned and its item becomes a one-key item on the ring slot, in arrays of the
+    // call's own (made only when some item hit); a set missed for the second time reserves a slot
+    // for k_blsw_apk_fill (one item of the call per set)
+    const bool use_apk = wave_small && n <= 1024 && kside && d.ar.on.load(std::memory_order_acquire);
+    ApkSlots as;
+    std::vector<uint32_t> a_off, a_cnt, a_idx, a_fill;  // a_fill: the fills' items, then their slots
+    uint64_t acount[4] = {0, 0, 0, 0};
+    if (use_apk) {
+        nwv::BlsApkRing& R = d.ar.ring;
+        as.ring = &R;
+        as.streams[0] = L.stream;
+        as.streams[1] = L.side[0];
+        std::vector<uint32_t> hit(n, nwv::BlsApkRing::NONE);
+        for (size_t i = 0; i < n; i++) {
+            if (!kmode[i] || !nwv::ApkKey::eligible(pk_cnt[i])) continue;
+            nwv::ApkKey k = nwv::ApkKey::make(remap.data() + pk_off[i], pk_cnt[i]);
+            const uint32_t s = R.lookup_pin(k);
+            if (s != nwv::BlsApkRing::NONE) {
+                hit[i] = s;
+                as.pinned.push_back(s);
+                acount[0]++;
+                continue;
+            }
+            acount[1]++;
+            bool mine = false;  // an earlier item of this call fills the set already
+            for (const ApkSlots::Fresh& f : as.fresh) mine = mine || f.key == k;
+            if (mine) continue;
+            bool noted = false;
+            const uint32_t r = R.miss(k, &noted);
+            if (noted) acount[2]++;
+            if (r != nwv::BlsApkRing::NONE) as.fresh.push_back({r, (uint32_t)i, std::move(k)});
+        }
+        if (acount[0]) {
+            a_off.assign(pk_off, pk_off + n);
+            a_cnt.assign(pk_cnt, pk_cnt + n);
+            a_idx = remap;
+            for (size_t i = 0; i < n; i++) {
+                if (hit[i] == nwv::BlsApkRing::NONE) continue;
+                a_off[i] = (uint32_t)a_idx.size();
+                a_cnt[i] = 1;
+                a_idx.push_back(AR_BASE + hit[i]);
+            }
+        }
+        for (const ApkSlots::Fresh& f : as.fresh) a_fill.push_back(f.item);
+        for (const ApkSlots::Fresh& f : as.fresh) a_fill.push_back(f.slot);
+    }
+    const size_t n_fill = as.fresh.size();
+    const bool a_hit = !a_idx.empty();
+    const uint32_t* k_off = a_hit ? a_off.data() : pk_off;
+    const uint32_t* k_cnt = a_hit ? a_cnt.data() : pk_cnt;
+    const std::vector<uint32_t>& k_idx = a_hit ? a_idx : remap;
+    const size_t nk_idx = k_idx.size();
     uint8_t seed[32];
     nwv_internal_fill_seed(nullptr, seed);  // the batch coefficients' key: OS entropy per call
     Arena a;
     const size_t o_keys = a.add(n_dec ? (const void*)fill_keys.data() : zero, 96 * n_dec + 8),
                  o_kslot = a.add(n_dec ? (const void*)fill_slot.data() : zero, 4 * n_dec + 4),
-                 o_sigs = a.add(sigs, 48 * n), o_off = a.add(pk_off, 4 * n), o_cnt = a.add(pk_cnt, 4 * n),
-                 o_idx = a.add(n_idx ? (const void*)remap.data() : zero, 4 * n_idx + 4),
+                 o_sigs = a.add(sigs, 48 * n), o_off = a.add(k_off, 4 * n), o_cnt = a.add(k_cnt, 4 * n),
+                 o_idx = a.add(nk_idx ? (const void*)k_idx.data() : zero, 4 * nk_idx + 4),
                  o_msg = a.add(msg_bytes ? (const void*)msg_base : zero, msg_bytes + 1),
                  o_moff = a.add(msg_off, 8 * n), o_mlen = a.add(msg_len, 4 * n), o_dst = a.add(dst, dl),
                  o_seed = a.add(seed, 32), o_kmode = a.add(kside ? (const void*)kmode.data() : zero, 4 * kmode.size() + 4),
                  o_scs = a.add(keep ? (const void*)kept.slots.data() : zero, 4 * kept.slots.size() + 4);
     // (one section for everything the ring adds: a single verification still fits stage_h2d's arguments)
     const size_t o_ring = use_ring ? a.add(rsec.data(), rsec.size()) : 0;
+    const size_t o_fill = n_fill ? a.add(a_fill.data(), 8 * n_fill) : 0;
     if ((rc = L.stage.ensure(al256(a.total) + 64 + 4 * wb_ng)) || (rc = L.in.ensure(a.total))) return rc;
     uint8_t* h = static_cast<uint8_t*>(L.stage.p);
     for (size_t k = 0; k < a.parts.size(); k++)
@@ -1765,7 +1897,9 @@ int verify_on(BlsDev& d, size_t n_keys, const uint8_t* keys, size_t n, const uin
               cached ? static_cast<const int32_t*>(d.kc.st.p) : nullptr, reinterpret_cast<uint32_t*>(w + w_krec),
               reinterpret_cast<int32_t*>(w + w_kst),
               cached && d.kc.lines_slots ? static_cast<const uint32_t*>(d.kc.lines.p) : nullptr,
-              cached ? static_cast<const uint32_t*>(d.kc.hrec.p) : nullptr};
+              cached ? static_cast<const uint32_t*>(d.kc.hrec.p) : nullptr,
+              use_apk ? static_cast<const uint32_t*>(d.ar.rec.p) : nullptr,
+              use_apk ? static_cast<const uint32_t*>(d.ar.lines.p) : nullptr};
     const uint32_t* km = kside ? reinterpret_cast<const uint32_t*>(in + o_kmode) : nullptr;
     auto* srec = reinterpret_cast<uint32_t*>(w + w_srec);
     auto* hrec = reinterpret_cast<uint32_t*>(w + w_hrec);
@@ -1841,6 +1975,7 @@ int verify_on(BlsDev& d, size_t n_keys, const uint8_t* keys, size_t n, const uin
                                reinterpret_cast<const uint32_t*>(in + o_off),
                                reinterpret_cast<const uint32_t*>(in + o_cnt),
                                reinterpret_cast<const uint32_t*>(in + o_idx), km, ajrec, sapk);
+        if (n_fill) BLS_HIP(hipEventRecord(L.sev[2], s1));
         BLS_HIP(trec(2, s1));
         BLS_HIP(trec(6, s1));
         BLS_HIP(trec(3, s0));
@@ -1856,6 +1991,16 @@ int verify_on(BlsDev& d, size_t n_keys, const uint8_t* keys, size_t n, const uin
                                reinterpret_cast<const uint32_t*>(in + o_ring + r_alen), (const uint8_t*)(in + o_dst),
                                (uint32_t)dl, static_cast<uint32_t*>(d.mr.rec.p),
                                reinterpret_cast<const uint32_t*>(in + o_ring + r_aslot));
+        // the aggregate-key fills on the main stream too, behind the key sums: they run beside the
+        // pairing kernel, which reads the sums and never the slots being filled
+        if (n_fill) {
+            BLS_HIP(hipStreamWaitEvent(s0, L.sev[2], 0));
+            hipLaunchKernelGGL(k_blsw_apk_fill, dim3((unsigned)n_fill), dim3(64), 0, s0, (uint32_t)n_fill,
+                               reinterpret_cast<const uint32_t*>(in + o_fill),
+                               reinterpret_cast<const uint32_t*>(in + o_fill + 4 * n_fill), (const uint32_t*)ajrec,
+                               (const int32_t*)sapk, static_cast<uint32_t*>(d.ar.rec.p),
+                               static_cast<uint32_t*>(d.ar.lines.p));
+        }
         kept.stream = s1;  // k_blsw_status writes the ring slots there
         // the rest runs on side 0 behind the hash, which ends after the signatures' decode (one
         // lane each, ~0.45 ms against ~0.57 ms): its wait on the decode is already met, so the
@@ -1882,7 +2027,7 @@ int verify_on(BlsDev& d, size_t n_keys, const uint8_t* keys, size_t n, const uin
         BLS_HIP(hipGetLastError());
         BLS_HIP(hipMemcpyAsync(status, st, 4 * n, hipMemcpyDeviceToHost, s1));
         BLS_HIP(hipStreamSynchronize(s1));
-        if (n_ah) BLS_HIP(hipStreamSynchronize(s0));
+        if (n_ah || n_fill) BLS_HIP(hipStreamSynchronize(s0));
         if (keep) {
             d.sc.publish(n, sigs, status, kept.slots);
             kept.sc = nullptr;
@@ -1892,6 +2037,11 @@ int verify_on(BlsDev& d, size_t n_keys, const uint8_t* keys, size_t n, const uin
         ms.finish(status, mcount);
         if (mstat)
             for (int k = 0; k < 5; k++) mstat[k] += mcount[k];
+        // a set is a function of the key cache's slots alone, but it is kept only behind a verified
+        // aggregate: peers cannot churn the ring without valid certificates
+        as.finish(status, acount);
+        if (astat)
+            for (int k = 0; k < 4; k++) astat[k] += acount[k];
         return finish(3);
     }
     if (!L.side[1] && hipStreamCreateWithFlags(&L.side[1], hipStreamNonBlocking) != hipSuccess)
@@ -2182,9 +2332,11 @@ __attribute__((visibility("hidden"))) int nwv_bls_device_counters(nwv_ctx* ctx, 
     return 6;
 }
 
-// the message-ring counters of the calling thread's last verify call on a context (nwv_bls_last_msgs)
+// the message-ring counters of the calling thread's last verify call on a context
+// (nwv_bls_last_msgs), and the aggregate-key ring's (nwv_bls_last_apk)
 struct MsgStat {
     uint64_t v[5] = {0, 0, 0, 0, 0};
+    uint64_t a[4] = {0, 0, 0, 0};
 };
 static thread_local std::unordered_map<const nwv_ctx*, MsgStat> t_last_msgs;
 
@@ -2198,7 +2350,7 @@ static int verify_many_impl(nwv_ctx* ctx, size_t n_keys, const uint8_t* keys, si
     if (n == 0) return NWV_OK;
     if (!sigs || !pk_off || !pk_cnt || !msg_off || !msg_len || !status || (n_keys && !keys))
         return nwv_internal_set_err(NWV_ERR_ARG, "null argument");
-    if (n > (1u << 26) || n_keys > (1u << 26)) return nwv_internal_set_err(NWV_ERR_ARG, "batch too large");
+    if (n > MAX_CALL_KEYS || n_keys > MAX_CALL_KEYS) return nwv_internal_set_err(NWV_ERR_ARG, "batch too large");
     dst = dst_or_default(dst, &dst_len);
     if (dst_len > 255) return nwv_internal_set_err(NWV_ERR_ARG, "DST longer than 255 bytes");
     // host-side shape checks: every key index and message range in bounds
@@ -2225,7 +2377,7 @@ static int verify_many_impl(nwv_ctx* ctx, size_t n_keys, const uint8_t* keys, si
     t_last_dev[ctx] = tickets[0].dev();
     if (ranges.size() == 1)
         return verify_on(*c->devs[tickets[0].dev()], n_keys, keys, n, sigs, pk_off, pk_cnt, pk_idx, n_idx, msg_base,
-                         msg_off, msg_len, msg_bytes, dst, dst_len, status, ah.n ? &ah : nullptr, mstat.v);
+                         msg_off, msg_len, msg_bytes, dst, dst_len, status, ah.n ? &ah : nullptr, mstat.v, mstat.a);
     std::vector<std::string> err(ranges.size());
     std::vector<MsgStat> rstat(ranges.size());  // (the ranges run on threads of their own)
     rc = bls_for_ranges(ranges, [&](size_t k, size_t lo, size_t hi) -> int {
@@ -2236,7 +2388,7 @@ static int verify_many_impl(nwv_ctx* ctx, size_t n_keys, const uint8_t* keys, si
         }
         const int e = verify_on(*c->devs[tickets[k].dev()], n_keys, keys, hi - lo, sigs + 48 * lo, pk_off + lo,
                                 pk_cnt + lo, pk_idx, ni, msg_base, msg_off + lo, msg_len + lo, mb, dst, dst_len,
-                                status + lo, nullptr, rstat[k].v);
+                                status + lo, nullptr, rstat[k].v, rstat[k].a);
         if (e) err[k] = nwv_last_error();
         return e;
     });
@@ -2244,8 +2396,10 @@ static int verify_many_impl(nwv_ctx* ctx, size_t n_keys, const uint8_t* keys, si
         for (size_t k = 0; k < err.size(); k++)
             if (!err[k].empty()) return nwv_internal_set_err(rc, err[k].c_str());
     if (rc) return rc;
-    for (const MsgStat& s : rstat)
+    for (const MsgStat& s : rstat) {
         for (int k = 0; k < 5; k++) mstat.v[k] += s.v[k];
+        for (int k = 0; k < 4; k++) mstat.a[k] += s.a[k];
+    }
     // a split call's ahead messages whose gates passed: hashed once the statuses are known, into
     // every device's ring (a range cannot read another range's statuses)
     if (ah.n) {
@@ -2353,6 +2507,57 @@ int nwv_bls_msg_ring_stats(nwv_ctx* ctx, uint64_t out[3]) {
     return NWV_OK;
 }
 
+int nwv_bls_set_apk_ring(nwv_ctx* ctx, size_t slots) {
+    BlsCtx* c;
+    int rc = ctx_of(ctx, &c);
+    if (rc) return rc;
+    if (slots > nwv::BlsApkRing::MAX_SLOTS)
+        return nwv_internal_set_err(NWV_ERR_ARG, "aggregate-key ring larger than 4,096 slots");
+    static std::mutex mu;  // one setter at a time
+    std::lock_guard<std::mutex> g(mu);
+    if (slots) {
+        for (BlsDev* d : c->devs)
+            if (d->ar.ring.cap() && d->ar.ring.cap() != slots)
+                return nwv_internal_set_err(NWV_ERR_ARG, "the aggregate-key ring's size is fixed once set");
+        for (BlsDev* d : c->devs) {
+            if (d->ar.ring.cap()) continue;
+            if (hipSetDevice(d->ordinal) != hipSuccess) return nwv_internal_set_err(NWV_ERR_HIP, "hipSetDevice (bls)");
+            if ((rc = d->ar.rec.ensure((size_t)4 * G2_REC_WORDS * slots)) ||
+                (rc = d->ar.lines.ensure((size_t)4 * KL_WORDS * slots)))
+                return rc;
+            d->ar.ring.init((uint32_t)slots);
+        }
+    }
+    for (BlsDev* d : c->devs) d->ar.on.store(slots != 0, std::memory_order_release);
+    return NWV_OK;
+}
+
+size_t nwv_bls_apk_ring(const nwv_ctx* ctx) {
+    BlsCtx* c;
+    if (ctx_of(const_cast<nwv_ctx*>(ctx), &c)) return 0;
+    BlsDev* d = c->devs[0];
+    return d->ar.on.load(std::memory_order_acquire) ? d->ar.ring.cap() : 0;
+}
+
+int nwv_bls_last_apk(nwv_ctx* ctx, uint64_t out[4]) {
+    if (!out) return nwv_internal_set_err(NWV_ERR_ARG, "null argument");
+    BlsCtx* c;
+    int rc = ctx_of(ctx, &c);
+    if (rc) return rc;
+    const auto it = t_last_msgs.find(ctx);
+    for (int k = 0; k < 4; k++) out[k] = it != t_last_msgs.end() ? it->second.a[k] : 0;
+    return NWV_OK;
+}
+
+int nwv_bls_apk_ring_stats(nwv_ctx* ctx, uint64_t out[3]) {
+    if (!out) return nwv_internal_set_err(NWV_ERR_ARG, "null argument");
+    BlsDev* d;
+    int rc = last_dev_of(ctx, &d);
+    if (rc) return rc;
+    d->ar.ring.counts(out);
+    return NWV_OK;
+}
+
 int nwv_bls_last_kernel_ms(nwv_ctx* ctx, double out_ms[5]) {
     if (!out_ms) return nwv_internal_set_err(NWV_ERR_ARG, "null argument");
     BlsDev* d;
@@ -2424,6 +2629,9 @@ int nwv_bls_keycache_reset(nwv_ctx* ctx) {
         std::unique_lock<std::shared_mutex> g(d->kc.mu);  // waits for calls that read the records
         d->kc.slot.clear();
         d->kc.used = 0;
+        // the aggregate-key ring's sets are lists of the slots just dropped: the same list will
+        // name other keys, so every set and the filter go, under the same hold
+        d->ar.ring.reset();
     }
     return NWV_OK;
 }

@@ -386,6 +386,19 @@ pub fn msg_ring_enable(slots: usize) -> Result<(), String> {
     }
 }
 
+/// Turn the engine's aggregate-key ring on with `slots` records per device (once, at start-up; 0
+/// switches it off again): a certificate by a signer set seen before -- a small committee has few
+/// quorums, certificates are validated and fetched again -- then verifies against the set's kept
+/// key sum and line table, like a header by a registered key.
+pub fn apk_ring_enable(slots: usize) -> Result<(), String> {
+    let rc = unsafe { ffi::nwv_bls_set_apk_ring(ctx(), slots) };
+    if rc == ffi::NWV_OK {
+        Ok(())
+    } else {
+        Err(last_error())
+    }
+}
+
 /// Hash messages into the ring ahead of the calls that verify over them.  The Proposer calls this
 /// with the certificate digest of the header it has just made: that header never passes
 /// `sanitize_header`, and its votes and certificate are the hits.  A no-op with the ring off.

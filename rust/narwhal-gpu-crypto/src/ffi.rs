@@ -371,6 +371,10 @@ extern "C" {
     ) -> c_int;
     pub fn nwv_bls_last_msgs(ctx: *mut NwvCtx, out: *mut u64) -> c_int;
     pub fn nwv_bls_msg_ring_stats(ctx: *mut NwvCtx, out: *mut u64) -> c_int;
+    pub fn nwv_bls_set_apk_ring(ctx: *mut NwvCtx, slots: usize) -> c_int;
+    pub fn nwv_bls_apk_ring(ctx: *const NwvCtx) -> usize;
+    pub fn nwv_bls_last_apk(ctx: *mut NwvCtx, out: *mut u64) -> c_int;
+    pub fn nwv_bls_apk_ring_stats(ctx: *mut NwvCtx, out: *mut u64) -> c_int;
     pub fn nwv_bls_keycache_register(ctx: *mut NwvCtx, n_keys: usize, keys: *const u8) -> c_int;
     pub fn nwv_bls_keycache_reset(ctx: *mut NwvCtx) -> c_int;
     pub fn nwv_bls_keycache_size(ctx: *mut NwvCtx) -> c_int;
