@@ -89,6 +89,30 @@ size_t nwv_bls_wave_batch_min(const nwv_ctx* ctx);
 /* the wave batch check of the last nwv_bls_verify_many call: out[0] groups formed, out[1] groups
  * that rejected, out[2] items re-checked per item (zeros when the check did not run) */
 int nwv_bls_last_batch(nwv_ctx* ctx, uint64_t out[3]);
+/* The key-transposed batch check: the same random linear combination regrouped by registered key.
+ * A large wave call (as above) of at least n items -- or a device's share of one -- groups its
+ * ELIGIBLE items (decode, G1 and key statuses OK, a signature that is not the identity, every key
+ * of the list in the serving device's key cache) into consecutive groups of NWV_BLS_KEY_GROUP
+ * items (env, read once; default 2,048).  A group over K distinct keys runs K + 1 Miller loops,
+ * each key's on its registered line table, and ONE final exponentiation, whatever its number of
+ * items.  A group whose distinct keys + 1 exceed a quarter of its items is not formed (env
+ * NWV_BLS_KEY_GROUP_RATIO, read once: the 4 of that rule; 0 forms every group) and its items run
+ * the per-item check, as do the OK items that are not eligible and the items of a group that
+ * rejects, so statuses stay exact.  When fewer than half of the call's OK items are eligible, or no
+ * group is formed, the call takes the path it takes with this setting at 0.  n = 0 (the default)
+ * turns it off: every call then takes exactly the launches it takes without this setting.  When
+ * this setting and nwv_bls_set_wave_batch_min both qualify, this one runs.  Every entry point that
+ * verifies through nwv_bls_verify_many inherits the setting.
+ * Two more codes of nwv_bls_last_path: 6 the check ran and every group accepted, 7 some group
+ * rejected and its items were then checked per item. */
+int nwv_bls_set_key_batch_min(nwv_ctx* ctx, size_t n);
+size_t nwv_bls_key_batch_min(const nwv_ctx* ctx);
+/* the key-transposed batch check of the calling thread's last nwv_bls_verify_many call (range 0's
+ * device when the call split): out[0] groups formed, out[1] groups that rejected, out[2] items of
+ * the groups that a per-item launch covered again, out[3] Miller loops the check ran (the groups'
+ * key entries plus one signature entry a group), out[4] items in the groups (zeros when the check
+ * did not run) */
+int nwv_bls_last_key_batch(nwv_ctx* ctx, uint64_t out[5]);
 /* keys of the last nwv_bls_verify_many call: out[0] key-list entries found in the key cache,
  * out[1] distinct keys the call decoded itself */
 int nwv_bls_last_keys(nwv_ctx* ctx, uint64_t out[2]);

@@ -109,6 +109,9 @@ def load():
         "nwv_bls_set_wave_batch_min": ([_vp, _sz], _i32),
         "nwv_bls_wave_batch_min": ([_vp], _sz),
         "nwv_bls_last_batch": ([_vp, _vp], _i32),
+        "nwv_bls_set_key_batch_min": ([_vp, _sz], _i32),
+        "nwv_bls_key_batch_min": ([_vp], _sz),
+        "nwv_bls_last_key_batch": ([_vp, _vp], _i32),
     }
     for name, (args, res) in sig.items():
         f = getattr(lib, name)

@@ -48,7 +48,7 @@ MSG_COUNTERS = ("hits_copied", "hits_chained", "computed", "published", "ahead_p
 NO_GATE = 0xFFFFFFFF
 KERNELS = ("keys_new_to_cache", "sig_decode", "hash_to_g1", "key_sums", "pairing_check")
 PATHS = ("per_item", "batch_accepted", "batch_rejected_then_per_item", "wave", "wave_batch_accepted",
-         "wave_batch_rejected_then_per_item")
+         "wave_batch_rejected_then_per_item", "key_batch_accepted", "key_batch_rejected_then_per_item")
 _bound = set()
 
 
@@ -211,6 +211,21 @@ class Bls:
         out = np.zeros(3, dtype=np.uint64)
         _lib._check(self.lib.nwv_bls_last_batch(self._h, out.ctypes.data))
         return int(out[0]), int(out[1]), int(out[2])
+
+    # the key-transposed batch check of large calls over registered keys (distinct keys + 1 Miller
+    # loops and one final exponentiation per group): off at 0; goes before the wave batch check
+    def set_key_batch_min(self, n):
+        _lib._check(self.lib.nwv_bls_set_key_batch_min(self._h, n))
+
+    def key_batch_min(self):
+        return int(self.lib.nwv_bls_key_batch_min(self._h))
+
+    def last_key_batch(self):
+        """(groups formed, groups rejected, group items re-checked per item, Miller loops of the
+        check, items in the groups) of the last verify_many"""
+        out = np.zeros(5, dtype=np.uint64)
+        _lib._check(self.lib.nwv_bls_last_key_batch(self._h, out.ctypes.data))
+        return tuple(int(x) for x in out)
 
     # the committee key cache: register at epoch start, reset at an epoch change
     def register_keys(self, keys):

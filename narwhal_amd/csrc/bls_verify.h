@@ -484,6 +484,17 @@ constexpr uint32_t WB_FAN = 17;  // records one wave multiplies at a tree level 
 // item i's points: p_out = [r] H as a homogeneous record (X Z, Y, Z^3 of the Jacobian multiple: the
 // form pair_flat takes with h_hom, no inversion), s_out = [r] sig (Jacobian record).  The two
 // multiplications are independent: the kernel gives each a lane of its own.
+// a Jacobian point as that homogeneous record; the identity as the neutral record
+NWV_HD void wb_store_hom(uint32_t* p_out, const jac<fp>& h) {
+    if (h.inf) {
+        st_g1j(p_out, h);
+        return;
+    }
+    st_fp(p_out, fp_mul(h.x, h.z));
+    st_fp(p_out + NL, h.y);
+    st_fp(p_out + 2 * NL, fp_mul(fp_sqr(h.z), h.z));
+    p_out[3 * NL] = 0u;
+}
 NWV_HD void wb_point_h(const uint32_t* h_rec, uint64_t r, uint32_t* p_out) {
     jac<fp> h;
     h.inf = true;
@@ -584,6 +595,29 @@ NWV_HD bool w_group_final(const W& w) {
     w.run(P_CONJ_F);
     final_exp(w);
     return w.f_is_one();
+}
+
+// ---- the key-transposed batch check (bls_key_batch.h): the same product regrouped
+// by key.  Every item of a group over registered keys contributes [r_i] H_i (Jacobian, so it can be
+// added: wb_point_s's form, on the hash record) once per occurrence of a key in its list to that
+// key's T_k; group g accepts iff (prod_k f(T_k, [h_eff] pk_k)) f(-S_g, g2) raised to the final
+// exponent is 1.  The Miller entries are those of the wave batch check: T_k as a homogeneous
+// record against key k's line table, S_g's entry as wb_sig_item writes it.
+//
+// lane `lane` of `lanes`' share of a key's sum: the records of hj (G1J_REC_WORDS each) at
+// cidx[lane], cidx[lane + lanes], ... below cnt, added in that order (jac_add: exact when two
+// occurrences name one point, as an item that lists a key twice does)
+NWV_HD jac<fp> kb_lane_sum(const uint32_t* hj, const uint32_t* cidx, uint32_t cnt, uint32_t lane, uint32_t lanes) {
+    jac<fp> acc;
+    acc.inf = true;
+    acc.x = acc.y = acc.z = fp_zero();
+    for (uint32_t c = lane; c < cnt; c += lanes) acc = jac_add(acc, ld_g1j(hj + (size_t)G1J_REC_WORDS * cidx[c]));
+    return acc;
+}
+// a key entry's Q record (the form the key sums' records take): the key's affine [h_eff] pk with Z = 1
+NWV_HD uint32_t kb_key_q_word(const uint32_t* key_rec, int wd) {
+    const fp one = k_one();
+    return wd < 4 * NL ? key_rec[wd] : wd < 5 * NL ? one.l[wd - 4 * NL] : 0u;
 }
 
 // ---- AggregateAuthenticator::aggregate (types/src/primary.rs:476-477) on a wave: g1_sum16 adds

@@ -38,6 +38,7 @@
 #include "bls_shard.h"
 #include "bls_msg_ring.h"
 #include "bls_apk_ring.h"
+#include "bls_key_batch.h"
 #include "place.h"
 #include "stage_args.h"
 
@@ -458,6 +459,10 @@ constexpr int BLS_PACK_MAX = 4;
 #ifndef NWV_BLS_BATCH_GROUP_DEFAULT
 #define NWV_BLS_BATCH_GROUP_DEFAULT 16
 #endif
+// eligible items per group of the key-transposed batch check (env NWV_BLS_KEY_GROUP overrides)
+#ifndef NWV_BLS_KEY_GROUP_DEFAULT
+#define NWV_BLS_KEY_GROUP_DEFAULT 2048
+#endif
 __device__ wave::SOp g_pair_script[2][wave::SCRIPT_MAX];  // [fixed key lines]
 __device__ int g_pair_script_n[2];
 // the Miller loop alone (wave::miller_script): the wave batch check's per-item pass
@@ -763,6 +768,97 @@ __global__ __launch_bounds__(BLS_LANES) void k_blsw_mark(uint32_t n, uint32_t gr
                                                          const uint32_t* inb, int32_t* st_pair) {
     BLS_IDX();
     if (inb[i]) st_pair[i] = gok[i / grp] == 1 ? ST_OK : ST_VERIFY_FAIL;
+}
+// The key-transposed batch check (bls_key_batch.h, bls_verify.h): the wave batch check's product
+// regrouped by registered key, K + 1 Miller loops a group of K distinct keys whatever its items.
+// The host's plan names the groups' items (`items`, group g at positions [g grp, (g + 1) grp)) and
+// every (group, key) entry's occurrences (coff / cidx, positions in `items`).
+//   k_blsk_rlc_pts   two lanes per position: [r_i] H_i and [r_i] sig_i, both Jacobian, r_i by the
+//                    caller's item index
+//   k_blsw_sfold     (the wave batch check's) S_g over the positions' [r_i] sig_i
+//   k_blsk_key_sums  one wave per key entry: T_k, the entry's hash side; the key's record as its Q
+//   k_blsk_sig_items one lane per group: S_g's entry behind the key entries
+//   k_blsw_mill_k    (the wave batch check's) every entry a one-key key-side item on its key's
+//                    registered line table
+//   k_blsk_ffold     k_blsw_ffold's tree over groups of unequal entry counts
+//   k_blsk_mark      st_pair of the groups' items from their group's verdict
+// Fail closed beyond the F records' counts: an item the plan names whose statuses the device does
+// not find OK (or whose signature is the identity), or an entry whose key's status is not OK,
+// poisons its group, and a poisoned group's last wave rejects.
+__global__ __launch_bounds__(BLS_LANES) void k_blsk_rlc_pts(uint32_t n, uint32_t grp, const uint32_t* items,
+                                                            const uint32_t* srec, const uint32_t* hrec,
+                                                            const int32_t* st_dec, const int32_t* st_apk,
+                                                            const uint8_t* seed, uint32_t* hj, uint32_t* sj,
+                                                            uint32_t* poison) {
+    const uint32_t t = blockIdx.x * BLS_LANES + threadIdx.x, e = t >> 1;
+    if (e >= n) return;
+    const uint32_t i = items[e];
+    const bool sig_side = (t & 1u) != 0;
+    const uint32_t* sr = srec + (size_t)G1_REC_WORDS * i;
+    uint32_t* out = (sig_side ? sj : hj) + (size_t)G1J_REC_WORDS * e;
+    if (st_dec[i] != ST_OK || st_apk[i] != ST_OK || sr[2 * NL]) {
+        wb_neutral_rec(out);
+        if (!sig_side) poison[e / grp] = 1u;
+        return;
+    }
+    wb_point_s(sig_side ? sr : hrec + (size_t)G1_REC_WORDS * i, rlc_scalar(seed, i), out);
+}
+__global__ __launch_bounds__(64) void k_blsk_key_sums(uint32_t n, const uint32_t* coff, const uint32_t* cidx,
+                                                      const uint32_t* eslot, const uint32_t* egrp, const uint32_t* hj,
+                                                      KeyTab kt, uint32_t* prec, uint32_t* arec, uint32_t* poison) {
+    __shared__ uint32_t xa[32 * G1J_REC_WORDS];
+    const uint32_t m = blockIdx.x;
+    if (m >= n) return;
+    const int lane = (int)threadIdx.x;
+    const uint32_t c0 = coff[m], slot = eslot[m];
+    jac<fp> acc = kb_lane_sum(hj, cidx + c0, coff[m + 1] - c0, (uint32_t)lane, 64u);
+#pragma unroll 1
+    for (int h = 32; h >= 1; h >>= 1) {
+        __syncthreads();
+        if (lane >= h && lane < 2 * h) st_g1j(xa + (lane - h) * G1J_REC_WORDS, acc);
+        __syncthreads();
+        if (lane < h) acc = jac_add(acc, ld_g1j(xa + lane * G1J_REC_WORDS));
+    }
+    const uint32_t* kr = kt.hrc + (size_t)G2_REC_WORDS * slot;
+    uint32_t* q = arec + (size_t)G2J_WORDS * m;
+    for (int wd = lane; wd < G2J_WORDS; wd += 64) q[wd] = kb_key_q_word(kr, wd);
+    if (lane != 0) return;
+    wb_store_hom(prec + (size_t)G1H_REC_WORDS * m, acc);
+    if (kt.sc[slot] != ST_OK) poison[egrp[m]] = 1u;
+}
+__global__ __launch_bounds__(BLS_LANES) void k_blsk_sig_items(uint32_t n, uint32_t grp, uint32_t n_ent,
+                                                              const uint32_t* sj, uint32_t* sgrec, uint32_t* prec,
+                                                              uint32_t* arec) {
+    BLS_IDX();
+    wb_sig_item(sj + (size_t)G1J_REC_WORDS * i * grp, sgrec + (size_t)G1_REC_WORDS * i,
+                prec + (size_t)G1H_REC_WORDS * (n_ent + i), arec + (size_t)G2J_WORDS * (n_ent + i));
+}
+// k_blsw_ffold with group g's records at positions p < keys: key entry goff[g] + p; p = keys: the
+// group's signature entry n_ent + g
+__global__ __launch_bounds__(64) void k_blsk_ffold(uint32_t ng, const uint32_t* goff, uint32_t n_ent, uint32_t wpg,
+                                                   uint32_t s, int last, uint32_t* frec, const uint32_t* poison,
+                                                   int32_t* gok) {
+    BLSW_LDS(wave::NSLOTS_PC);
+    const uint32_t g = blockIdx.x / wpg, wv = blockIdx.x % wpg;
+    if (g >= ng) return;
+    const uint32_t e0 = goff[g], keys = goff[g + 1] - e0, m = keys + 1, p0 = wv * WB_FAN * s;
+    if (p0 >= m) return;
+    const wave::Wave w{wm, (int)threadIdx.x};
+    auto at = [&](uint32_t p) { return frec + (size_t)FB_REC_WORDS * (p < keys ? e0 + p : n_ent + g); };
+    const uint32_t cnt = w_ffold_step(w, at, p0, s, m, WB_FAN);
+    if (last) {
+        const bool ok = w_group_final(w);
+        if (threadIdx.x == 0) gok[g] = (ok && cnt == m && poison[g] == 0u) ? 1 : 0;
+        return;
+    }
+    uint32_t* o = at(p0);
+    w.get_words(wave::REG_F, o, 12);
+    if (threadIdx.x == 0) o[12 * NL] = cnt;
+}
+__global__ __launch_bounds__(BLS_LANES) void k_blsk_mark(uint32_t n, uint32_t grp, const uint32_t* items,
+                                                         const int32_t* gok, int32_t* st_pair) {
+    BLS_IDX();
+    st_pair[items[i]] = gok[i / grp] == 1 ? ST_OK : ST_VERIFY_FAIL;
 }
 // the flat scripts into g_pair_script on the calling thread's device, once per device
 static int ensure_pair_script() {
@@ -1151,6 +1247,11 @@ struct BlsLane {
     hipStream_t side[2] = {nullptr, nullptr};  // keys + key sums (+ hash to G1 on small wave calls); hash to G1
     HBuf stage;
     DBuf in, work;
+    // the key-transposed batch check's own buffers (sized by the plan, made after the pre-pairing
+    // kernels: the call's arena and scratch never move under it): the statuses and verdicts on
+    // the host, the plan's lists on both sides, the check's records
+    HBuf kb_st, kb_up;
+    DBuf kb_in, kb_work;
     // [0,1] keys, [1,2] key sums (side 0); [3,4] signatures (main); [5,6] hash to G1 (side 1; side
     // 0 on small wave calls); [7,8] pairing check (main); [9] inputs resident, [10] side 0 done,
     // [11] side 1 done.  side[1] is created by the first call that needs it: a lane of small wave
@@ -1382,6 +1483,11 @@ struct BlsDev {
     // nwv_bls_set_wave_batch_min: large wave calls of at least this many items take the wave batch
     // check (0: never)
     std::atomic<size_t> wave_batch_min{0};
+    // nwv_bls_set_key_batch_min: large wave calls of at least this many items take the
+    // key-transposed batch check (0: never); it goes before the wave batch check
+    std::atomic<size_t> key_batch_min{0};
+    // its last call: groups formed, rejected, items re-checked, Miller loops, items in the groups
+    uint64_t last_kbatch[5] = {0, 0, 0, 0, 0};
 };
 // the BLS engine's state of one context: one BlsDev per device of the context (nwv_init with
 // several devices shards nwv_bls_verify_many by item index, bls_shard.h).  Diagnostic / test hook:
@@ -1675,6 +1781,20 @@ int verify_on(BlsDev& d, size_t n_keys, const uint8_t* keys, size_t n, const uin
     const size_t wb_min = d.wave_batch_min.load(std::memory_order_relaxed);
     const bool wbatch = wavem && !wave_small && wb_min > 0 && n >= wb_min;
     const size_t wb_ng = wbatch ? (n + wb_grp - 1) / wb_grp : 0, wb_m = wbatch ? n + wb_ng : 0;
+    // the key-transposed batch check (bls_key_batch.h): large wave calls of at least
+    // nwv_bls_set_key_batch_min items; groups of kb_grp eligible items, a group dropped when its
+    // distinct keys + 1 exceed 1 / kb_ratio of its items (0: never)
+    static const uint32_t kb_grp = [] {
+        const char* e = std::getenv("NWV_BLS_KEY_GROUP");
+        const unsigned long v = e ? std::strtoul(e, nullptr, 10) : (unsigned long)NWV_BLS_KEY_GROUP_DEFAULT;
+        return (uint32_t)(v < 1 ? 1 : v > 65536 ? 65536 : v);
+    }();
+    static const uint32_t kb_ratio = [] {
+        const char* e = std::getenv("NWV_BLS_KEY_GROUP_RATIO");
+        const unsigned long v = e ? std::strtoul(e, nullptr, 10) : 4ul;
+        return (uint32_t)(v > 1024 ? 1024 : v);
+    }();
+    const size_t kb_min = d.key_batch_min.load(std::memory_order_relaxed);
     int rc;
     // the call's key table: cache slots (lookups only) or scratch entries KC_CAP + j
     std::shared_lock<std::shared_mutex> kc_hold(d.kc.mu);  // records stay put while our kernels read them
@@ -1925,7 +2045,7 @@ int verify_on(BlsDev& d, size_t n_keys, const uint8_t* keys, size_t n, const uin
     bool untimed = false;  // a small call that recorded no stage events (set on that path only)
     auto trec = [&](int k, hipStream_t s) { return no_timing ? hipSuccess : hipEventRecord(L.ev[k], s); };
     // stage times of the completed call, its path and key counts -> the device's "last call"
-    uint64_t wb_stat[3] = {0, 0, 0};
+    uint64_t wb_stat[3] = {0, 0, 0}, kb_stat[5] = {0, 0, 0, 0, 0};
     auto finish = [&](int path_done) -> int {
         const int pairs[5][2] = {{0, 1}, {3, 4}, {5, 6}, {1, 2}, {7, 8}};  // keys, sigs, h2c, apk, pairing
         double ms5[5] = {0, 0, 0, 0, 0};
@@ -1940,6 +2060,7 @@ int verify_on(BlsDev& d, size_t n_keys, const uint8_t* keys, size_t n, const uin
         d.last_keys[0] = hits;
         d.last_keys[1] = n_dec;
         std::memcpy(d.last_batch, wb_stat, sizeof wb_stat);
+        std::memcpy(d.last_kbatch, kb_stat, sizeof kb_stat);
         return NWV_OK;
     };
     BLS_HIP(nwv_stage::stage_h2d(in, h, a.total, s0));  // small calls: through kernel arguments
@@ -2103,7 +2224,9 @@ int verify_on(BlsDev& d, size_t n_keys, const uint8_t* keys, size_t n, const uin
             const char* e = std::getenv("NWV_BLS_LDS_PAD");
             return e ? (size_t)std::strtoull(e, nullptr, 10) : (size_t)0;
         }();
-        if ((pack > 1 || wbatch) && ensure_pair_script()) return NWV_ERR_HIP;
+        // (every item's keys cached is what the key side already asks: kside)
+        const bool kb_cand = !wave_small && kside && kb_min > 0 && n >= kb_min;
+        if ((pack > 1 || wbatch || kb_cand) && ensure_pair_script()) return NWV_ERR_HIP;
         const auto* d_off = reinterpret_cast<const uint32_t*>(in + o_off);
         const auto* d_cnt = reinterpret_cast<const uint32_t*>(in + o_cnt);
         const auto* d_idx = reinterpret_cast<const uint32_t*>(in + o_idx);
@@ -2124,7 +2247,111 @@ int verify_on(BlsDev& d, size_t n_keys, const uint8_t* keys, size_t n, const uin
                                    km ? km + lo : nullptr, spair + lo);
         };
         int path_done = 3;
-        if (wbatch) {
+        bool kb_done = false;
+        if (kb_cand) {
+            // the pre-pairing statuses come back first: the plan groups the items they leave
+            if ((rc = L.kb_st.ensure(12 * n + 64))) return rc;
+            int32_t* h_dec = static_cast<int32_t*>(L.kb_st.p);
+            int32_t *h_apk = h_dec + n, *h_gok = h_apk + n;
+            BLS_HIP(hipMemcpyAsync(h_dec, sdec, 4 * n, hipMemcpyDeviceToHost, s0));
+            BLS_HIP(hipMemcpyAsync(h_apk, sapk, 4 * n, hipMemcpyDeviceToHost, s0));
+            BLS_HIP(hipStreamSynchronize(s0));
+            std::vector<uint8_t> ok(n), el(n);
+            for (size_t i = 0; i < n; i++) {
+                ok[i] = h_dec[i] == ST_OK && h_apk[i] == ST_OK;
+                // (a compressed identity has bit 6 of its first byte set; the kernels check again)
+                el[i] = ok[i] && kmode[i] && !(sigs[48 * i] & 0x40);
+            }
+            nwv::KeyBatchPlan P;
+            nwv::key_batch_plan(n, ok.data(), el.data(), pk_off, pk_cnt, remap.data(), d.kc.used, kb_grp, kb_ratio, P);
+            if (P.run) {
+                const size_t ne = P.items.size(), ng = P.groups(), M = P.entries(), C = P.cidx.size(), KM = M + ng;
+                // the plan's lists, one copy: items | goff | eslot | egrp | coff | cidx | 0..M-1 | ones
+                const size_t u_goff = ne, u_eslot = u_goff + ng + 1, u_egrp = u_eslot + M, u_coff = u_egrp + M,
+                             u_cidx = u_coff + M + 1, u_iota = u_cidx + C, u_ones = u_iota + M, u_end = u_ones + M;
+                if ((rc = L.kb_up.ensure(4 * u_end)) || (rc = L.kb_in.ensure(4 * u_end))) return rc;
+                uint32_t* up = static_cast<uint32_t*>(L.kb_up.p);
+                std::memcpy(up, P.items.data(), 4 * ne);
+                std::memcpy(up + u_goff, P.goff.data(), 4 * (ng + 1));
+                std::memcpy(up + u_eslot, P.eslot.data(), 4 * M);
+                std::memcpy(up + u_egrp, P.egrp.data(), 4 * M);
+                std::memcpy(up + u_coff, P.coff.data(), 4 * (M + 1));
+                std::memcpy(up + u_cidx, P.cidx.data(), 4 * C);
+                for (size_t m = 0; m < M; m++) {
+                    up[u_iota + m] = (uint32_t)m;
+                    up[u_ones + m] = 1u;
+                }
+                const uint32_t* ki = static_cast<const uint32_t*>(L.kb_in.p);
+                BLS_HIP(hipMemcpyAsync(L.kb_in.p, up, 4 * u_end, hipMemcpyHostToDevice, s0));
+                // the check's records: [r] H and [r] sig per position, S_g per group, the Miller
+                // entries' hash sides, Qs and F records, the groups' poison and verdict words
+                const size_t k_sj = al256(4 * G1J_REC_WORDS * ne), k_sg = al256(k_sj + 4 * G1J_REC_WORDS * ne),
+                             k_p = al256(k_sg + 4 * G1_REC_WORDS * ng), k_q = al256(k_p + 4 * G1H_REC_WORDS * KM),
+                             k_f = al256(k_q + 4 * G2J_WORDS * KM), k_poi = al256(k_f + 4 * FB_REC_WORDS * KM),
+                             k_gok = k_poi + 4 * ng, k_end = k_gok + 4 * ng + 4;
+                if ((rc = L.kb_work.ensure(k_end))) return rc;
+                uint8_t* kw = static_cast<uint8_t*>(L.kb_work.p);
+                auto* khj = reinterpret_cast<uint32_t*>(kw);
+                auto* ksj = reinterpret_cast<uint32_t*>(kw + k_sj);
+                auto* ksg = reinterpret_cast<uint32_t*>(kw + k_sg);
+                auto* kp = reinterpret_cast<uint32_t*>(kw + k_p);
+                auto* kq = reinterpret_cast<uint32_t*>(kw + k_q);
+                auto* kf = reinterpret_cast<uint32_t*>(kw + k_f);
+                auto* kpoi = reinterpret_cast<uint32_t*>(kw + k_poi);
+                auto* kgok = reinterpret_cast<int32_t*>(kw + k_gok);
+                const uint32_t G = kb_grp, gmax = (uint32_t)std::min<size_t>(G, ne);
+                uint32_t kmax = 0;
+                for (size_t g = 0; g < ng; g++) kmax = std::max(kmax, P.goff[g + 1] - P.goff[g]);
+                BLS_HIP(hipMemsetAsync(kpoi, 0, 8 * ng, s0));  // no poison; a group whose tree does not finish stays rejected
+                hipLaunchKernelGGL(k_blsk_rlc_pts, dim3(kBlocks(2 * ne)), dim3(BLS_LANES), 0, s0, (uint32_t)ne, G, ki,
+                                   (const uint32_t*)srec, (const uint32_t*)hrec, (const int32_t*)sdec,
+                                   (const int32_t*)sapk, (const uint8_t*)(in + o_seed), khj, ksj, kpoi);
+                for (uint32_t m = gmax; m > 1; m = (m + 1) / 2)
+                    hipLaunchKernelGGL(k_blsw_sfold, dim3(kBlocks(ng * ((m + 1) / 2))), dim3(BLS_LANES), 0, s0,
+                                       (uint32_t)ne, G, (uint32_t)ng, m, ksj);
+                hipLaunchKernelGGL(k_blsk_key_sums, dim3((unsigned)M), dim3(64), 0, s0, (uint32_t)M, ki + u_coff,
+                                   ki + u_cidx, ki + u_eslot, ki + u_egrp, (const uint32_t*)khj, kt, kp, kq, kpoi);
+                hipLaunchKernelGGL(k_blsk_sig_items, dim3(kBlocks(ng)), dim3(BLS_LANES), 0, s0, (uint32_t)ng, G,
+                                   (uint32_t)M, (const uint32_t*)ksj, ksg, kp, kq);
+                // every key entry as a one-key key-side item of its own: key list entry m = slot eslot[m]
+                const MillArgs ma{(uint32_t)M, ksg, ki + u_ones, kf};
+                hipLaunchKernelGGL(k_blsw_mill_k, dim3((unsigned)((KM + pack - 1) / pack)), dim3(64),
+                                   (size_t)4 * (wave::KP_WORDS + pack * wave::SW * wave::NSLOTS_PC) + lds_pad, s0,
+                                   (uint32_t)KM, pack, ma, (const uint32_t*)kp, (const uint32_t*)kq, kt, ki + u_iota,
+                                   ki + u_ones, ki + u_eslot, ki + u_ones);
+                for (uint32_t s = 1;; s *= WB_FAN) {
+                    const uint32_t ents = (kmax + 1 + s - 1) / s, wpg = (ents + WB_FAN - 1) / WB_FAN;
+                    hipLaunchKernelGGL(k_blsk_ffold, dim3((unsigned)(ng * wpg)), dim3(64), 0, s0, (uint32_t)ng,
+                                       ki + u_goff, (uint32_t)M, wpg, s, wpg == 1 ? 1 : 0, kf, (const uint32_t*)kpoi, kgok);
+                    if (wpg == 1) break;
+                }
+                hipLaunchKernelGGL(k_blsk_mark, dim3(kBlocks(ne)), dim3(BLS_LANES), 0, s0, (uint32_t)ne, G, ki,
+                                   (const int32_t*)kgok, spair);
+                BLS_HIP(hipGetLastError());
+                BLS_HIP(hipMemcpyAsync(h_gok, kgok, 4 * ng, hipMemcpyDeviceToHost, s0));
+                BLS_HIP(hipStreamSynchronize(s0));
+                // per item: the OK items outside the groups and every rejected group's items, in
+                // shared launches as the wave batch check shares them
+                std::vector<uint8_t> need(n, 0), ing(n, 0);
+                for (uint32_t i : P.outside) need[i] = 1;
+                for (uint32_t i : P.items) ing[i] = 1;
+                for (size_t g = 0; g < ng; g++) {
+                    if (h_gok[g] == 1) continue;
+                    kb_stat[1]++;
+                    for (uint32_t p = P.gfirst[g]; p < P.gfirst[g + 1]; p++) need[P.items[p]] = 1;
+                }
+                for (const auto& r : nwv::key_batch_ranges(n, need.data(), 1024)) {
+                    per_item_range(r.first, r.second - r.first);
+                    for (size_t i = r.first; i < r.second; i++) kb_stat[2] += ing[i];
+                }
+                kb_stat[0] = ng;
+                kb_stat[3] = KM;
+                kb_stat[4] = ne;
+                path_done = kb_stat[1] ? 7 : 6;
+                kb_done = true;
+            }
+        }
+        if (!kb_done && wbatch) {
             auto* wf = reinterpret_cast<uint32_t*>(w + w_wf);
             auto* wp = reinterpret_cast<uint32_t*>(w + w_wp);
             auto* wj = reinterpret_cast<uint32_t*>(w + w_wj);
@@ -2181,7 +2408,7 @@ int verify_on(BlsDev& d, size_t n_keys, const uint8_t* keys, size_t n, const uin
                 g = e;
             }
             path_done = wb_stat[1] ? 5 : 4;
-        } else {
+        } else if (!kb_done) {
             per_item_range(0, n);
         }
         BLS_HIP(hipEventRecord(L.ev[8], s0));
@@ -2597,6 +2824,30 @@ int nwv_bls_last_batch(nwv_ctx* ctx, uint64_t out[3]) {
     if (rc) return rc;
     std::lock_guard<std::mutex> g(d->stat_mu);
     for (int k = 0; k < 3; k++) out[k] = d->last_batch[k];
+    return NWV_OK;
+}
+
+int nwv_bls_set_key_batch_min(nwv_ctx* ctx, size_t n) {
+    BlsCtx* c;
+    int rc = ctx_of(ctx, &c);
+    if (rc) return rc;
+    for (BlsDev* d : c->devs) d->key_batch_min.store(n, std::memory_order_relaxed);
+    return NWV_OK;
+}
+
+size_t nwv_bls_key_batch_min(const nwv_ctx* ctx) {
+    BlsCtx* c;
+    if (ctx_of(const_cast<nwv_ctx*>(ctx), &c)) return 0;
+    return c->devs[0]->key_batch_min.load(std::memory_order_relaxed);
+}
+
+int nwv_bls_last_key_batch(nwv_ctx* ctx, uint64_t out[5]) {
+    if (!out) return nwv_internal_set_err(NWV_ERR_ARG, "null argument");
+    BlsDev* d;
+    int rc = last_dev_of(ctx, &d);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> g(d->stat_mu);
+    for (int k = 0; k < 5; k++) out[k] = d->last_kbatch[k];
     return NWV_OK;
 }
 

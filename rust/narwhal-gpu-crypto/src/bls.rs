@@ -399,6 +399,37 @@ pub fn apk_ring_enable(slots: usize) -> Result<(), String> {
     }
 }
 
+/// Let large verification calls (more than 1,024 items) of at least `n` items over registered
+/// committee keys take the key-transposed batch check: one Miller loop per distinct key of a group
+/// plus one, and one final exponentiation a group, whatever the number of items (0, the default,
+/// switches it off).  Statuses stay exact: a group that rejects is checked per item.
+pub fn key_batch_min_set(n: usize) -> Result<(), String> {
+    let rc = unsafe { ffi::nwv_bls_set_key_batch_min(ctx(), n) };
+    if rc == ffi::NWV_OK {
+        Ok(())
+    } else {
+        Err(last_error())
+    }
+}
+
+/// The setting `key_batch_min_set` made (0: off).
+pub fn key_batch_min() -> usize {
+    unsafe { ffi::nwv_bls_key_batch_min(ctx()) }
+}
+
+/// Of the calling thread's last verification call: groups formed, groups rejected, group items
+/// checked again per item, Miller loops the check ran, items in the groups (zeros when the
+/// key-transposed batch check did not run).
+pub fn last_key_batch() -> Result<[u64; 5], String> {
+    let mut out = [0u64; 5];
+    let rc = unsafe { ffi::nwv_bls_last_key_batch(ctx(), out.as_mut_ptr()) };
+    if rc == ffi::NWV_OK {
+        Ok(out)
+    } else {
+        Err(last_error())
+    }
+}
+
 /// Hash messages into the ring ahead of the calls that verify over them.  The Proposer calls this
 /// with the certificate digest of the header it has just made: that header never passes
 /// `sanitize_header`, and its votes and certificate are the hits.  A no-op with the ring off.
