@@ -45,7 +45,12 @@ hostemu: tests/_build/libhostemu.so tests/_build/libsvcstub.so tests/_build/libb
 	tests/_build/libplace.so tests/_build/libkcalloc.so tests/_build/libgroupkeys.so tests/_build/libeachemu.so \
 	tests/_build/libblswbemu.so tests/_build/libblsmsgring.so tests/_build/libblsmremu.so \
 	tests/_build/libblsapkring.so tests/_build/libblsaremu.so tests/_build/libblskeybatch.so \
-	tests/_build/libblskbemu.so
+	tests/_build/libblskbemu.so tests/_build/libblswvemu.so
+# the wave interpreter one program at a time with its limb bounds evaluated (BLS_BOUNDS_CHECK;
+# tests/test_bls_wave_vectors_hostemu.py)
+tests/_build/libblswvemu.so: tests/hostemu/bls_wave_vectors_hostemu.cpp $(BLS_SRC) $(BLS_SHARED)
+	@mkdir -p tests/_build
+	$(HIPCC) -std=c++17 -O2 --offload-host-only -x hip -DBLS_BOUNDS_CHECK -fPIC -shared -o $@ tests/hostemu/bls_wave_vectors_hostemu.cpp
 # the key-transposed batch check's host pass (bls_key_batch.h) with no HIP (tests/test_bls_key_batch_host.py)
 tests/_build/libblskeybatch.so: tests/hostemu/bls_key_batch_stub.cpp narwhal_amd/csrc/bls_key_batch.h
 	@mkdir -p tests/_build
@@ -139,7 +144,11 @@ tests/_build/libfoldemu.so: tests/hostemu/fold_hostemu.cpp $(CSRC)
 	$(HIPCC) -std=c++17 -O1 --offload-host-only -x hip -DNWV_BOUNDS_CHECK -fPIC -shared -o $@ tests/hostemu/fold_hostemu.cpp
 
 tools: tools/ubench_valu tools/ubench_field tools/ubench_wave tools/ubench_row tools/ubench_prep tools/libsvcbench.so \
-	tools/fe_vectors
+	tools/fe_vectors tools/bls_wave_vectors
+# the device's wave interpreter, fp_inv_wave and the F == 1 verdicts on slot images from a file
+# (tests/test_gpu_bls_wave_vectors.py)
+tools/bls_wave_vectors: tools/bls_wave_vectors.hip $(BLS_SRC)
+	$(HIPCC) --offload-arch=$(ARCH) -O3 -std=c++17 -o $@ $<
 # the device's fe_mul / fe_sq / fe_sqn on limb vectors from a file (tests/test_gpu_fe_seeded.py)
 tools/fe_vectors: tools/fe_vectors.hip narwhal_amd/csrc/fe25519.h
 	$(HIPCC) --offload-arch=$(ARCH) -O3 -std=c++17 -o $@ $<

@@ -33,6 +33,36 @@
 #define BLS_NOINLINE __host__ __device__ __attribute__((noinline))
 #endif
 
+// BLS_BOUNDS_CHECK (host test builds only, tests/hostemu/bls_wave_vectors_hostemu.cpp): the limb
+// bounds that the comments of this file and of bls_wave.h state are evaluated on every call and a
+// miss is counted (not aborted on: the test reports what fired); undefined, BLS_BOUND is nothing.
+#ifdef BLS_BOUNDS_CHECK
+#ifdef __HIP_DEVICE_COMPILE__
+#error "BLS_BOUNDS_CHECK is for host builds (--offload-host-only)"
+#endif
+namespace bls {
+struct BoundsStats {
+    uint64_t fired;         // bound assertions that did not hold
+    uint64_t par_fallback;  // carry_par calls that took the sequential pass
+    uint64_t top_negative;  // combinations whose top limb sum was negative
+    const char* first;      // the first assertion that fired
+};
+inline BoundsStats& bounds_stats() {
+    static BoundsStats s = {0, 0, 0, nullptr};
+    return s;
+}
+}  // namespace bls
+#define BLS_BOUND(cond)                                  \
+    do {                                                 \
+        if (!(cond)) {                                   \
+            ::bls::BoundsStats& s_ = ::bls::bounds_stats(); \
+            if (!s_.fired++) s_.first = #cond;           \
+        }                                                \
+    } while (0)
+#else
+#define BLS_BOUND(cond) ((void)0)
+#endif
+
 namespace bls {
 
 constexpr int NL = 14;
@@ -133,8 +163,40 @@ NWV_HD bool fp_is_zero(const fp& a) {
 }
 NWV_HD bool fp_eq(const fp& a, const fp& b) { return fp_is_zero(fp_sub(a, b)); }
 
+#ifdef BLS_BOUNDS_CHECK
+// fp_mul's / fp_sqr's column sums again in 128 bits (the sums only grow, so each is looked at after
+// every row added to it): none passes 64 bits, and the last, the result's top limb, fits 32
+inline void mul_columns_check(const fp& a, const fp& b, bool sqr) {
+    typedef unsigned __int128 u128;
+    const fp P = k_p();
+    u128 c[2 * NL];
+    for (int k = 0; k < 2 * NL; k++) c[k] = 0;
+    for (int i = 0; i < NL; i++) {
+        if (sqr) BLS_BOUND(a.l[i] < (1u << 31));  // a2[i] = a.l[i] << 1 in 32 bits
+        for (int j = 0; j < NL; j++) c[i + j] += (u128)((uint64_t)a.l[i] * b.l[j]);
+    }
+    for (int k = 0; k < 2 * NL; k++) BLS_BOUND((c[k] >> 64) == 0);
+    for (int i = 0; i < NL; i++) {
+        const uint32_t m = ((uint32_t)c[i] * BLS_N0) & LM;
+        for (int j = 0; j < NL; j++) {
+            c[i + j] += (u128)((uint64_t)m * P.l[j]);
+            BLS_BOUND((c[i + j] >> 64) == 0);
+        }
+        c[i + 1] += c[i] >> 28;
+        BLS_BOUND((c[i + 1] >> 64) == 0);
+    }
+    for (int k = NL; k < 2 * NL - 1; k++) {
+        c[k + 1] += c[k] >> 28;
+        BLS_BOUND((c[k + 1] >> 64) == 0);
+    }
+    BLS_BOUND((c[2 * NL - 1] >> 32) == 0);
+}
+#endif
 // Montgomery product a b / 2^392 mod p; a, b < 2p with limbs < 2^28 -> result < 2p, limbs < 2^28
 BLS_HD fp fp_mul(const fp& a, const fp& b) {
+#ifdef BLS_BOUNDS_CHECK
+    mul_columns_check(a, b, false);
+#endif
     const fp P = k_p();
     uint64_t c[2 * NL];
 #pragma unroll
@@ -160,6 +222,9 @@ BLS_HD fp fp_mul(const fp& a, const fp& b) {
     return r;
 }
 BLS_HD fp fp_sqr(const fp& a) {
+#ifdef BLS_BOUNDS_CHECK
+    mul_columns_check(a, a, true);  // the same column totals: 2 a_i a_j from the doubled limb
+#endif
     const fp P = k_p();
     uint64_t c[2 * NL];
     uint32_t a2[NL];

@@ -139,6 +139,9 @@ NWV_HD void acc_n(const wword* wm, const Rec& r, uint64_t* a) {
 }
 // at most G terms' reads in flight at once (8: all of a section's; 4 halves the registers they
 // hold, for the packed pairing kernel, which must fit two waves per SIMD)
+#ifndef NWV_BLS_PAIR_TERMS
+#define NWV_BLS_PAIR_TERMS 4  // the packed pairing kernel's G
+#endif
 template <int BASE, int G = 8>
 NWV_HD void acc_terms(const wword* wm, const Rec& r, int n, uint64_t* a) {
     if (G < 8 && n > G) {
@@ -164,11 +167,41 @@ NWV_HD void acc_terms(const wword* wm, const Rec& r, int n, uint64_t* a) {
         default: break;
     }
 }
+#ifdef BLS_BOUNDS_CHECK
+// the packed pairs' precondition, every limb's positive (offset included) and negative sum on its
+// own in 64 bits: each below 2^32 (no half carries into its neighbour) and, below the top limb,
+// the difference non-negative; a negative top limb sum is counted
+template <int BASE>
+inline void comb_bounds_check(const wword* wm, const wword* kpt, const Rec& r, int np, int nn, uint32_t k1) {
+    uint64_t ps[NL], ns[NL];
+    for (int j = 0; j < NL; j++) {
+        ps[j] = k1 ? kpt[NL * (k1 - 1) + j] : 0u;
+        ns[j] = 0;
+    }
+    for (int u = 0; u < np; u++) {
+        const uint32_t w = rec_u16(r, BASE + u);
+        for (int j = 0; j < NL; j++) ps[j] += (uint64_t)wm[SW * (w & 0xfffu) + j] << (w >> 12);
+    }
+    for (int u = 0; u < nn; u++) {
+        const uint32_t w = rec_u16(r, BASE + TMAX + u);
+        for (int j = 0; j < NL; j++) ns[j] += (uint64_t)wm[SW * (w & 0xfffu) + j] << (w >> 12);
+    }
+    for (int j = 0; j < NL; j++) {
+        BLS_BOUND((ps[j] >> 32) == 0);
+        BLS_BOUND((ns[j] >> 32) == 0);
+        if (j < NL - 1) BLS_BOUND(ps[j] >= ns[j]);
+    }
+    if (ps[NL - 1] < ns[NL - 1]) bounds_stats().top_negative++;
+}
+#endif
 // the limb sums of a combination: positive terms + 2^k p - negative terms (the subtraction per
 // 32-bit limb: with the redundant offset no limb below the top goes negative)
 // (kpt: the P << k table, KP_WORDS words; a one-item wave keeps it just below slot 0)
 template <int BASE, int G = 8>
 NWV_HD void comb_sums(const wword* wm, const wword* kpt, const Rec& r, int np, int nn, uint32_t k1, uint32_t* out) {
+#ifdef BLS_BOUNDS_CHECK
+    comb_bounds_check<BASE>(wm, kpt, r, np, nn, k1);
+#endif
     uint64_t a[NL / 2];
     if (k1) {
         const wword2* kp = reinterpret_cast<const wword2*>(kpt + NL * (k1 - 1));
@@ -212,18 +245,30 @@ NWV_HD fp carry_seq(const uint32_t* a) {
         c = d >> 28;
     }
     v.l[NL - 1] = a[NL - 1] + c;
+    BLS_BOUND((int32_t)v.l[NL - 1] >= 0);  // the value is never negative
     return v;
 }
 // a product operand: limbs below 2^28 + 16, each from its own sum and the one below (no carry
-// chain); fp_mul takes such limbs.  A negative top limb (possible only for a value within 2^-24 of
-// a multiple of 2^364) takes the sequential pass.
+// chain); fp_mul takes such limbs.  The top limb comes out negative (-1) when the top limb sum is
+// negative and the carry that makes the value non-negative arrives through the chain: the value
+// then has top limb 0 and limb 12 below 16 (it is below 2^341), and the sequential pass is taken.
+// No pairing on random points gets there, but ordinary edge values do: a combination
+// 0 - x + 2^k p with x at its bound (x = 2p - 1 under the offset 2p leaves 1).  The vectors of
+// tests/bls_wave_vectors.py take this branch 292 times in 95 of 1,731 program runs (10 of the 47
+// programs; a top limb sum is negative in 150 runs), uniform inputs below 2p never
+// (tests/test_bls_wave_vectors_hostemu.py, BLS_BOUNDS_CHECK counts both).
 NWV_HD fp carry_par(const uint32_t* a) {
     fp v;
     v.l[0] = a[0] & LM;
 #pragma unroll
     for (int j = 1; j < NL - 1; j++) v.l[j] = (a[j] & LM) + (a[j - 1] >> 28);
     v.l[NL - 1] = a[NL - 1] + (a[NL - 2] >> 28);
+#ifdef BLS_BOUNDS_CHECK
+    if ((int32_t)v.l[NL - 1] < 0) bounds_stats().par_fallback++;
+#endif
     if ((int32_t)v.l[NL - 1] < 0) v = carry_seq(a);
+    for (int j = 0; j < NL - 1; j++) BLS_BOUND(v.l[j] <= (1u << 28) + 16);
+    BLS_BOUND((int32_t)v.l[NL - 1] >= 0);
     return v;
 }
 // a combination as a normalised value (the tests' and the G1/G2 helpers' form)
@@ -250,6 +295,14 @@ NWV_HD fp quick_reduce(const fp& x) {
         c = d >> 28;
     }
     r.l[NL - 1] = (uint32_t)((int32_t)x.l[NL - 1] - (int32_t)(q * P.l[NL - 1]) - (int32_t)hi + c);
+#ifdef BLS_BOUNDS_CHECK
+    {
+        fp t;
+        BLS_BOUND((int32_t)x.l[NL - 1] >= 0);
+        BLS_BOUND((int32_t)r.l[NL - 1] >= 0 && r.l[NL - 1] <= LM);
+        BLS_BOUND(limb_sub(t, r, k_p2()) != 0);  // r < 2p
+    }
+#endif
     return r;
 }
 
@@ -349,54 +402,17 @@ __device__ __attribute__((noinline)) void wave_run(uint32_t* wm_generic, int lan
         s = wrap ? 0 : s + 1;
     }
 }
-// k items on one wave (the throughput path): item j's slots in bank j (the one-item layout: P << k
-// below its slot 0), banks `bank` words apart.  A stage of nl lanes per item runs 64 / nl items per
-// pass (lane l: item l / nl of the pass, record l % nl), ceil(k / (64 / nl)) passes, then one wave
-// sync.  So the narrow stages -- the final exponentiation's cyclotomic squarings (18 products, then
-// 12 combinations), which are most of a pairing check's stages -- run k items for the instructions
-// of one, and a wide one (an Fp12 product's 54) takes k passes as k waves would.  The pairing
-// kernel's time did not move with 4 instead of 10 resident waves per CU (LDS padded per wave, 37.5
-// ms for 16,384 items either way, profiles/round5_bls_occupancy.txt): one wave per SIMD already
-// keeps its VALU busy, so fewer instructions per item is what raises throughput.
-__device__ __attribute__((noinline)) void wave_run_k(uint32_t* wm0_generic, uint32_t bank, int k, int lane,
-                                                     uint32_t off, int n, int nl0, int reps) {
-    wword* wm0 = (wword*)wm0_generic;
-    const uint16_t* base0 = T_DATA + off;
-    const uint16_t* base = base0;
-    int nl = nl0;
-    Rec cur = load_rec(base0 + (uint32_t)(lane % nl0) * REC);
-    const int total = n * reps;
-#pragma unroll 1
-    for (int t = 0, s = 0; t < total; t++) {
-        Hdr h = rec_hdr(cur);
-        h.nap = __builtin_amdgcn_readfirstlane(h.nap);
-        h.nan = __builtin_amdgcn_readfirstlane(h.nan);
-        h.nbp = __builtin_amdgcn_readfirstlane(h.nbp);
-        h.nbn = __builtin_amdgcn_readfirstlane(h.nbn);
-        const bool wrap = s + 1 == n;
-        const int nl_next = wrap ? nl0 : __builtin_amdgcn_readfirstlane(h.nl_next);
-        const uint16_t* nbase = wrap ? base0 : base + (uint32_t)nl * REC;
-        Rec nxt = cur;
-        if (t + 1 < total) nxt = load_rec(nbase + (uint32_t)(lane % nl_next) * REC);
-        const int ipp = 64 / nl, first = lane / nl;
-        if (first < ipp) {
-            const uint32_t dst = rec_u16(cur, 0);
-#pragma unroll 1
-            for (int item = first; item < k; item += ipp) {
-                wword* wm = wm0 + (uint32_t)item * bank;
-                const fp v = lane_value(wm, h, cur);
-#pragma unroll
-                for (int j = 0; j < NL; j++) wm[SW * dst + j] = v.l[j];
-            }
-        }
-        wsync();
-        base = nbase;
-        nl = nl_next;
-        cur = nxt;
-        s = wrap ? 0 : s + 1;
-    }
-}
-// The Wave interface over k banks (final_exp, exp_chain and cyc_exp_x run on it unchanged)
+// k items on one wave (the throughput path): item j's slots in bank j, banks `bank` words apart,
+// behind one shared P << k table.  The stage loop over the banks is the packed kernel's own, inline
+// in pair_flat (nwv_bls.hip): a stage of nl lanes per item runs 64 / nl items per pass (lane l: item
+// l / nl of the pass, record l % nl), ceil(k / (64 / nl)) passes, then one wave sync.  So the narrow
+// stages -- the final exponentiation's cyclotomic squarings (18 products, then 12 combinations),
+// which are most of a pairing check's stages -- run k items for the instructions of one, and a wide
+// one (an Fp12 product's 54) takes k passes as k waves would.  The pairing kernel's time did not
+// move with 4 instead of 10 resident waves per CU (LDS padded per wave, 37.5 ms for 16,384 items
+// either way, profiles/round5_bls_occupancy.txt): one wave per SIMD already keeps its VALU busy, so
+// fewer instructions per item is what raises throughput.
+// The banks' set-up, inversion and verdict (what pair_flat runs between its stages)
 struct WaveK {
     uint32_t* wm;   // bank 0's slot 0
     uint32_t bank;  // words from one bank to the next
@@ -404,7 +420,6 @@ struct WaveK {
     int lane;
     __device__ uint32_t* bk(int j) const { return wm + (uint32_t)j * bank; }
     __device__ void sync() const { wsync(); }
-    __device__ void run(Prog p, int reps = 1) const { wave_run_k(wm, bank, k, lane, p.off, p.n, p.nl0, reps); }
     __device__ void zero(int slot, int n) const {
         for (int j = 0; j < k; j++)
             for (int w = lane; w < SW * n; w += 64) bk(j)[SW * slot + w] = 0;

@@ -451,8 +451,8 @@ __device__ __forceinline__ void blsw_pair_item(uint32_t* wm, uint32_t i, const u
 //
 // The whole check is one loop over the flat script of wave::pairing_script (g_pair_script, one per
 // line mode): the stage loop below is the kernel's only copy of the interpreter and the loop makes
-// no calls, so no callee-saved registers go through scratch (round 5's out-of-line wave_run_k
-// wrote ~616 KB of scratch per item).  The banks share one P << k table at the front of the LDS
+// no calls, so no callee-saved registers go through scratch (round 5's out-of-line interpreter
+// call wrote ~616 KB of scratch per item).  The banks share one P << k table at the front of the LDS
 // (9.6 KB a bank instead of 10.5 KB).
 constexpr int BLS_PACK_MAX = 4;
 // items per group of the wave batch check (env NWV_BLS_BATCH_GROUP overrides)
@@ -468,16 +468,14 @@ __device__ int g_pair_script_n[2];
 // the Miller loop alone (wave::miller_script): the wave batch check's per-item pass
 __device__ wave::SOp g_mill_script[2][wave::SCRIPT_MAX];
 __device__ int g_mill_script_n[2];
-// two waves per SIMD (<= 256 registers: at most 4 terms' LDS reads in flight, NWV_BLS_PAIR_TERMS)
+// two waves per SIMD (<= 256 registers: at most 4 terms' LDS reads in flight, NWV_BLS_PAIR_TERMS
+// of bls_wave.h)
 // with three items a wave (NWV_BLS_PACK: 3 x 6.5 KB banks -- registers never live together share
 // slots, tools/gen_bls_wave.py PC_ALIAS -- + the shared 0.9 KB table = 8 waves per CU): 16,384
 // checks 23.5 -> 16.0 ms against one wave per SIMD with three 10.5 KB banks
 // (profiles/round6_bls_pair_sweep.txt)
 #ifndef NWV_BLS_PAIR_WAVES
 #define NWV_BLS_PAIR_WAVES 2
-#endif
-#ifndef NWV_BLS_PAIR_TERMS
-#define NWV_BLS_PAIR_TERMS 4
 #endif
 // x / d and x % d for 0 <= x <= 64 and a wave-uniform 1 <= d <= 64 without a division sequence:
 // x ceil(2^16 / d) >> 16 is exact there (the error x (ceil(2^16/d) - 2^16/d) / 2^16 < 1/1024 < 1/d)
@@ -602,7 +600,7 @@ __device__ __forceinline__ void pair_flat(uint32_t* lds_k, uint32_t i0, int k, c
             w.sync();
             continue;
         }
-        // RUN: the program's stages, `reps` times over (wave_run_k's loop, inline: the one copy)
+        // RUN: the program's stages, `reps` times over (wave_run's loop over the banks: the one copy)
         const uint16_t* base0 = T_DATA + op.a;
         const uint16_t* base = base0;
         const int np = (int)(op.b & 0xffffu), nl0 = (int)(op.b >> 16), total = np * (int)(op.c & 0xffffu);
