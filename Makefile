@@ -45,7 +45,7 @@ hostemu: tests/_build/libhostemu.so tests/_build/libsvcstub.so tests/_build/libb
 	tests/_build/libplace.so tests/_build/libkcalloc.so tests/_build/libgroupkeys.so tests/_build/libeachemu.so \
 	tests/_build/libblswbemu.so tests/_build/libblsmsgring.so tests/_build/libblsmremu.so \
 	tests/_build/libblsapkring.so tests/_build/libblsaremu.so tests/_build/libblskeybatch.so \
-	tests/_build/libblskbemu.so tests/_build/libblswvemu.so
+	tests/_build/libblskbemu.so tests/_build/libblswvemu.so tests/_build/libcombpassemu.so
 # the wave interpreter one program at a time with its limb bounds evaluated (BLS_BOUNDS_CHECK;
 # tests/test_bls_wave_vectors_hostemu.py)
 tests/_build/libblswvemu.so: tests/hostemu/bls_wave_vectors_hostemu.cpp $(BLS_SRC) $(BLS_SHARED)
@@ -123,6 +123,10 @@ tests/_build/libhostemu.so: tests/hostemu/hostemu.cpp $(CSRC)
 tests/_build/libcombemu.so: tests/hostemu/comb_hostemu.cpp $(CSRC)
 	@mkdir -p tests/_build
 	$(HIPCC) -std=c++17 -O1 --offload-host-only -x hip -DNWV_BOUNDS_CHECK -fPIC -shared -o $@ tests/hostemu/comb_hostemu.cpp
+# the comb pass kernel's per-signature arithmetic on the host (tests/test_comb_pass_hostemu.py)
+tests/_build/libcombpassemu.so: tests/hostemu/comb_pass_hostemu.cpp tests/hostemu/comb_hostemu.cpp $(CSRC)
+	@mkdir -p tests/_build
+	$(HIPCC) -std=c++17 -O1 --offload-host-only -x hip -DNWV_BOUNDS_CHECK -fPIC -shared -o $@ tests/hostemu/comb_pass_hostemu.cpp
 # the row kernel's per-signature arithmetic on the host (tests/test_each_row_hostemu.py)
 tests/_build/libeachemu.so: tests/hostemu/each_row_hostemu.cpp $(CSRC)
 	@mkdir -p tests/_build

@@ -146,6 +146,23 @@ int nwv_diag_each_row(const nwv_ctx* ctx, uint64_t out[2]);
  * flags instead of decompressing and hashing again, unless the context was opened with
  * NWV_FLAG_NO_MSM_REUSE.  verify_each and keyed batches always run the plain form. */
 int nwv_diag_each_row_reuse(const nwv_ctx* ctx, uint64_t* out);
+/* Largest per-signature pass that takes the comb pass kernel: when a single-device keyed batch of
+ * more than 64 and at most n signatures whose keys all have a comb table (nwv_keycache_register)
+ * goes through the batch MSM and the MSM does not accept it, the pass that names the bad set
+ * (verdict bits asked for, or the MSM undetermined) runs in one launch of k_ed_comb_pass -- every
+ * signature's [s]B - [k]A summed from B's comb and its key's, the same exact ZIP-215 verdicts --
+ * instead of the row kernel or the lane pipeline, unless the context was opened with
+ * NWV_FLAG_NO_TINY, NWV_FLAG_MSM_ALWAYS or NWV_FLAG_MSM_NEVER.  An accepted batch launches what it
+ * launches without it.  Staged batches (nwv_stage_*) and batches that take k_ed_comb
+ * (nwv_set_comb_batch_max) are not affected.  Default 0 (off).  Same semantics as
+ * nwv_set_each_row_max: values at or above the shard minimum are clamped to just below it, the
+ * getter returns the value in force. */
+int nwv_set_comb_pass_max(nwv_ctx* ctx, size_t n);
+size_t nwv_comb_pass_max(const nwv_ctx* ctx);
+/* Diagnostics, summed over the devices: out[0] per-signature passes run by k_ed_comb_pass (each of
+ * them also counts as a per-signature pass in nwv_diag_counters out[2] and
+ * nwv_diag_device_counters [8], and never as a comb batch), out[1] the signatures in those passes. */
+int nwv_diag_comb_pass(const nwv_ctx* ctx, uint64_t out[2]);
 /* HIP ordinal of the context's i-th device (-1 if out of range) */
 int nwv_device_ordinal(const nwv_ctx* ctx, int i);
 /* Placement: which device object of a multi-device context serves a call.  A call that does not

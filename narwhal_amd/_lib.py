@@ -117,9 +117,12 @@ def load():
         f = getattr(lib, name)
         f.argtypes = args
         f.restype = res
-    # the aggregate-key ring's entry points (narwhal_amd.bls wraps them); an older build selected
-    # with NWV_LIB for an A/B run lacks them, and calling one there still raises
+    # the aggregate-key ring's entry points (narwhal_amd.bls wraps them) and the comb pass's; an
+    # older build selected with NWV_LIB for an A/B run lacks them, and calling one there still raises
     newer = {
+        "nwv_set_comb_pass_max": ([_vp, _sz], _i32),
+        "nwv_comb_pass_max": ([_vp], _sz),
+        "nwv_diag_comb_pass": ([_vp, _vp], _i32),
         "nwv_bls_set_apk_ring": ([_vp, _sz], _i32),
         "nwv_bls_apk_ring": ([_vp], _sz),
         "nwv_bls_last_apk": ([_vp, _vp], _i32),
@@ -284,6 +287,21 @@ class Engine:
         """nwv_diag_each_row: (per-signature passes run by k_ed_each_row, signatures in them)"""
         out = np.zeros(2, dtype=np.uint64)
         _check(self.lib.nwv_diag_each_row(self._h, out.ctypes.data))
+        return int(out[0]), int(out[1])
+
+    def set_comb_pass_max(self, n):
+        """nwv_set_comb_pass_max: the largest rejected registered-key batch whose bad set the comb
+        pass kernel names (0: off, the default)"""
+        _check(self.lib.nwv_set_comb_pass_max(self._h, int(n)))
+
+    @property
+    def comb_pass_max(self):
+        return int(self.lib.nwv_comb_pass_max(self._h))
+
+    def diag_comb_pass(self):
+        """nwv_diag_comb_pass: (per-signature passes run by k_ed_comb_pass, signatures in them)"""
+        out = np.zeros(2, dtype=np.uint64)
+        _check(self.lib.nwv_diag_comb_pass(self._h, out.ctypes.data))
         return int(out[0]), int(out[1])
 
     def diag_each_row_reuse(self):

@@ -1,8 +1,9 @@
 // comb.h -- lane-level pieces of the per-signature comb check (comb_kernels.hip k_ed_comb): the
 // equation of k_ed_tiny (tiny_kernels.hip), [8] R = [8]([s]B - [k]A) with [s]B - [k]A summed from
-// the fixed-base combs of B and of the registered key, for keyed batches above TINY_MAX.
-// Everything here is __host__ __device__: the kernel calls these functions and
-// tests/hostemu/comb_hostemu.cpp runs the same ones on the CPU.
+// the fixed-base combs of B and of the registered key, for keyed batches above TINY_MAX, and of
+// the same check as a per-signature pass behind a rejected batch MSM (k_ed_comb_pass4 / 16).
+// Everything here is __host__ __device__: the kernels call these functions and
+// tests/hostemu/comb_hostemu.cpp and comb_pass_hostemu.cpp run the same ones on the CPU.
 #pragma once
 #include "ed25519_lane.h"
 #include "msm.h"
@@ -52,6 +53,56 @@ NWV_HD bool comb_cross_equal(const uint32_t x[32]) {
     bool id = true;
     for (int q = 0; q < 8; q++) id = id && x[q] == x[8 + q] && x[16 + q] == x[24 + q];
     return id;
+}
+
+// ---- k_ed_comb_pass (comb_kernels.hip): the same check with the comb sum walked by lanes ----
+// COMB_PASS_G signatures a workgroup; L lanes a signature (4 or 16), each lane 64 / L consecutive
+// digit positions of both combs.
+static constexpr int COMB_PASS_G = 16;
+
+// Entry |d| of table j of a comb as a mixed-addition operand, negated when neg; a zero digit gives
+// the neutral record (1 | 1 | 0) by selection from entry 1's load, so lanes of a wave never branch
+// on a digit.
+NWV_HD ge_precomp comb_record(const uint32_t* comb, int j, int d, bool neg) {
+    const int m = d < 0 ? -d : d;
+    const ge_precomp q = msm_load_point(comb + MSM_PT_WORDS * (COMB_ENTRIES * j + (m ? m - 1 : 0)), neg);
+    const bool z = m == 0;
+    return ge_precomp{fe_select(q.ypx, fe_one(), z), fe_select(q.ymx, fe_one(), z), fe_select(q.xy2d, fe_zero(), z)};
+}
+
+// One lane's share of [s]B - [k]A: positions j0 .. j0 + cnt - 1 (ds, dk: the digits from position
+// j0 on).  The sum is seeded from position j0's B record (msm_point_seed; the neutral record seeds
+// the identity as (0 : 2 : 2 : 0)), every other record joins by a mixed addition.
+NWV_HD ge_p3 comb_lane_sum(const uint32_t* bcomb, const uint32_t* acomb, int j0, int cnt, const int* ds,
+                           const int* dk) {
+    ge_p3 P = msm_point_seed(comb_record(bcomb, j0, ds[0], ds[0] < 0));
+    P = ge_p1p1_to_p3(ge_madd(P, comb_record(acomb, j0, dk[0], dk[0] > 0)));
+#pragma unroll 1
+    for (int p = 1; p < cnt; p++) {
+        P = ge_p1p1_to_p3(ge_madd(P, comb_record(bcomb, j0 + p, ds[p], ds[p] < 0)));
+        P = ge_p1p1_to_p3(ge_madd(P, comb_record(acomb, j0 + p, dk[p], dk[p] > 0)));
+    }
+    return P;
+}
+
+// One level of the join of a signature's lane sums: the lane keeps its sum plus its partner's
+// (level o: lane t, t a multiple of 2 o, takes lane t + o's).
+NWV_HD ge_p3 comb_join(const ge_p3& mine, const ge_p3& theirs) { return p3_add(mine, theirs); }
+
+// [8] R = [8] P projectively from the joined sum P (doubled three times here) and r8 = X | Y | Z of
+// [8] R (ten limbs each): comb_cross's four products, compared as canonical words.
+NWV_HD bool comb_pass_equal(const ge_p3& P, const uint32_t* r8) {
+    const ge_p3 P8 = p3_dbl_n(P, 3);
+    const fe rz = load_fe(r8 + 20);
+    uint32_t a[8], b[8];
+    fe_freeze(fe_mul(P8.X, rz), a);
+    fe_freeze(fe_mul(load_fe(r8), P8.Z), b);
+    bool eq = true;
+    for (int q = 0; q < 8; q++) eq = eq && a[q] == b[q];
+    fe_freeze(fe_mul(P8.Y, rz), a);
+    fe_freeze(fe_mul(load_fe(r8 + 10), P8.Z), b);
+    for (int q = 0; q < 8; q++) eq = eq && a[q] == b[q];
+    return eq;
 }
 
 }  // namespace nwv

@@ -152,3 +152,134 @@ extern "C" __global__ void __launch_bounds__(64 * COMB_WAVES) k_ed_comb(CombArgs
     }
 #endif
 }
+
+// ---- the comb check as a per-signature pass behind a rejected batch MSM (k_ed_comb_pass) ----
+// The verdict is k_ed_comb's, signature by signature; the layout is for passes of thousands of
+// signatures.  COMB_PASS_G = 16 signatures a workgroup, three roles on waves of their own:
+//   wave 0            lanes 0..15 hash one signature each (comb.h comb_scalars: k, s < l, the
+//                     digits of s and k into LDS)
+//   waves 1..4        decompress four R's each, one per 16-lane row, from the first instruction
+//                     (nothing here waits for the hash), then double each three times by rows
+//   the sum waves     after the one barrier: L lanes a signature, lane t walks digit positions
+//                     64 t / L .. 64 (t + 1) / L - 1 of both combs with mixed additions
+//                     (comb_lane_sum; a zero digit adds the neutral record, no branch), the lane
+//                     sums join in log2 L levels through lane shuffles (comb_join), and the
+//                     signature's first lane doubles three times, compares with [8] R
+//                     (comb_pass_equal) and ors the verdict bit into the batch's verdict words
+// L = 4: one sum wave (six waves a workgroup); L = 16: four (nine waves).  LDS holds the digits,
+// the decompression rows and the [8] R records only: the partial sums stay in registers.
+// The host zeroes the verdict words on the stream before the launch: a signature whose workgroup
+// never ran stays rejected.
+struct CombPassArgs {
+    const uint8_t* pk;      // [n][32] each signature's key (the hash's A bytes)
+    const uint8_t* sig;     // [n][64]
+    const uint8_t* msg;     // message arena; off[n] / len[n] index it
+    const uint64_t* off;
+    const uint32_t* len;
+    const uint32_t* kc;     // key cache records: word MSM_PT_WORDS - 1 of a slot = A did not decode
+    const uint32_t* combs;  // per-key comb tables (COMB_WORDS words each)
+    const uint32_t* bcomb;  // B's comb table
+    const uint32_t* kslot;  // [n] signature i's key cache slot
+    const uint32_t* cidx;   // [n] signature i's comb table
+    unsigned long long* verdict;  // [ceil(n / 64)] zero at launch; bit i = signature i accepted
+    uint32_t n;
+};
+
+static constexpr int COMB_PASS_DEC = COMB_PASS_G / 4;  // decompression waves
+template <int L>
+struct CombPassShape {
+    static constexpr int SUM = COMB_PASS_G * L / 64;  // sum waves
+    static constexpr int WAVES = 1 + COMB_PASS_DEC + SUM;
+};
+
+template <int L>
+__device__ __forceinline__ void comb_pass_block(const CombPassArgs& a) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    constexpr int G = COMB_PASS_G, DEC = COMB_PASS_DEC;
+    __shared__ uint32_t rsh[G * 48];               // four rows (48 words each) a decompression wave
+    __shared__ uint32_t r8sh[DEC * 48];            // [8] R of one row on its way to ten-limb form
+    __shared__ uint32_t rrec[G * 32];              // per signature [8] R: X | Y | Z; word 31: 1 = R does not decode
+    __shared__ int dg[G][2][COMB_TABLES];          // digits of s and of k
+    __shared__ uint32_t hok[G];                    // s < l
+    const int t = threadIdx.x, wv = t >> 6, lane = t & 63;
+    const uint32_t base = blockIdx.x * G;  // grid = ceil(n / G); base < n
+    const int cnt = (int)(a.n - base < (uint32_t)G ? a.n - base : (uint32_t)G);  // live signatures
+    if (wv == 0) {
+        if (lane < cnt) {
+            const uint32_t i = base + lane;
+            uint32_t Aw[8], Rw[8], Sw[8];
+            msm_load8(a.pk + 32 * (size_t)i, Aw);
+            msm_load8(a.sig + 64 * (size_t)i, Rw);
+            msm_load8(a.sig + 64 * (size_t)i + 32, Sw);
+            hok[lane] = comb_scalars(Aw, Rw, Sw, a.msg + a.off[i], a.len[i], dg[lane][0], dg[lane][1]) ? 1u : 0u;
+        }
+    } else if (wv <= DEC) {
+        const int first = 4 * (wv - 1);  // the wave's rows hold signatures first .. first + 3
+        if (first < cnt) {               // (wave-uniform)
+            const int row = lane >> 4, limb = lane & 15;
+            uint32_t y16 = 0u;  // rows past the end decompress y = 0; nobody reads them
+            if (first + row < cnt) y16 = reinterpret_cast<const uint16_t*>(a.sig + 64 * (size_t)(base + first + row))[limb];
+            uint32_t* wsh = rsh + 192 * (wv - 1);
+            const bool ok = row_decompress(y16, lane, row, limb, wsh + 48 * row);
+            if (limb == 0) rrec[32 * (first + row) + 31] = ok ? 0u : 1u;
+            // [8] R, one R after the other, as k_ed_comb's wave 0 does: every row loads row q's
+            // record and the wave doubles it three times from (2x : 2y : 2)
+            rowf::RowConsts k = rowf::row_consts();
+            k.rot = 1;
+            uint32_t* w8 = r8sh + 48 * (wv - 1);
+#pragma unroll 1
+            for (int q = 0; q < 4 && first + q < cnt; q++) {
+                const uint32_t ypx = wsh[48 * q + limb], ymx = wsh[48 * q + 16 + limb];
+                rowf::RowP3 d{rowf::carry32(rowf::sub(ypx, ymx, k), k), rowf::carry32(ypx + ymx, k),
+                              rowf::sel(rowf::limb_is(0), 0u, 2u), 0u};
+#pragma unroll 1
+                for (int r2 = 0; r2 < 3; r2++) d = rowf::row_dbl(d, k);
+                rowf::lds_order();
+                if (row == 0) {
+                    w8[limb] = d.X;
+                    w8[16 + limb] = d.Y;
+                    w8[32 + limb] = d.Z;
+                }
+                rowf::lds_order();
+                if (lane < 3) store_fe(&rrec[32 * (first + q) + 10 * lane], fe_from_limbs16(w8 + 16 * lane));  // X | Y | Z
+                rowf::lds_order();
+            }
+        }
+    }
+    __syncthreads();  // digits and every [8] R in LDS
+    if (wv > DEC) {
+        constexpr int P = COMB_TABLES / L;  // positions a lane
+        const int grp = (wv - DEC - 1) * (64 / L) + lane / L, sub = lane % L;
+        // lanes of a signature past the end run the last live one's arithmetic (every read stays
+        // in bounds, the wave stays uniform) and store nothing
+        const int gl = grp < cnt ? grp : cnt - 1;
+        const uint32_t i = base + (uint32_t)gl;
+        const uint32_t* ct = a.combs + (size_t)COMB_WORDS * a.cidx[i];
+        ge_p3 S = comb_lane_sum(a.bcomb, ct, P * sub, P, dg[gl][0] + P * sub, dg[gl][1] + P * sub);
+#pragma unroll 1
+        for (int o = 1; o < L; o <<= 1) {
+            // every lane adds lane + o's sum; those of lanes t = 0 mod 2 o are the tree's
+            ge_p3 T;
+            for (int q = 0; q < 10; q++) {
+                T.X.v[q] = __shfl(S.X.v[q], (lane + o) & 63);
+                T.Y.v[q] = __shfl(S.Y.v[q], (lane + o) & 63);
+                T.Z.v[q] = __shfl(S.Z.v[q], (lane + o) & 63);
+                T.T.v[q] = __shfl(S.T.v[q], (lane + o) & 63);
+            }
+            S = comb_join(S, T);
+        }
+        const bool eq = comb_pass_equal(S, rrec + 32 * gl);
+        if (sub == 0 && grp < cnt) {
+            const bool aok = a.kc[(size_t)KC_SLOT_WORDS * a.kslot[i] + MSM_PT_WORDS - 1] == 0u;
+            if (eq && aok && hok[gl] && rrec[32 * gl + 31] == 0u) atomicOr(a.verdict + (i >> 6), 1ull << (i & 63));
+        }
+    }
+#endif
+}
+
+extern "C" __global__ void __launch_bounds__(64 * CombPassShape<4>::WAVES) k_ed_comb_pass4(CombPassArgs a) {
+    comb_pass_block<4>(a);
+}
+extern "C" __global__ void __launch_bounds__(64 * CombPassShape<16>::WAVES) k_ed_comb_pass16(CombPassArgs a) {
+    comb_pass_block<16>(a);
+}

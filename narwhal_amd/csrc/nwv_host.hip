@@ -157,6 +157,9 @@ struct EdBuffers {
     // signature's key cache slot and comb table, staged with the batch (views into the arena)
     bool comb = false;
     DevBuf comb_slot, comb_cidx;
+    // the same arrays staged for the per-signature pass alone (ed_stage_keyed, nwv_set_comb_pass_max):
+    // the batch takes the MSM, and k_ed_comb_pass names the bad set if the MSM does not accept
+    bool comb_pass = false;
     void release() {
         for (DevBuf* b : {&pk, &sig, &msg, &off, &len, &kbuf, &flags, &tables, &verdict, &m_scal,
                           &m_partial, &m_state, &m_pts, &m_digits, &m_cnt, &m_tiles, &m_entries,
@@ -168,6 +171,7 @@ struct EdBuffers {
         tables_ready = false;
         tiny = false;
         comb = false;
+        comb_pass = false;
     }
 };
 
@@ -267,6 +271,11 @@ struct Gpu {
     std::atomic<size_t> each_row_max{0};
     // (n_each_row_msm: those of them that reused a rejected MSM's records, nwv_diag_each_row_reuse)
     std::atomic<uint64_t> n_each_row{0}, n_each_row_sigs{0}, n_each_row_msm{0};
+    // per-signature passes of at most comb_pass_max signatures behind a keyed MSM over registered
+    // keys take k_ed_comb_pass (the context's value, nwv_set_comb_pass_max; 0: off), and how many
+    // did (nwv_diag_comb_pass): passes, signatures
+    std::atomic<size_t> comb_pass_max{0};
+    std::atomic<uint64_t> n_comb_pass{0}, n_comb_pass_sigs{0};
 };
 
 int with_device(Lane& d) {
@@ -1053,6 +1062,7 @@ struct KeyedTail {
     // k_ed_comb's per-signature tables (n key cache slots, n comb table indices), or null
     const uint32_t* sig_slot = nullptr;
     const uint32_t* sig_cidx = nullptr;
+    bool pass_only = false;  // the tables are for k_ed_comb_pass behind the MSM, not for k_ed_comb
 };
 
 int ed_stage(Lane& d, EdBuffers& b, size_t lo, size_t hi, const uint8_t* pk, const uint8_t* sig,
@@ -1107,6 +1117,7 @@ int ed_stage(Lane& d, EdBuffers& b, size_t lo, size_t hi, const uint8_t* pk, con
     b.tables_ready = false;
     b.tiny = false;
     b.comb = false;
+    b.comb_pass = false;
     // large stagings: the caller's pk / sig / message bytes are packed piece by piece with each
     // piece's DMA queued at once (pack_copy_h2d); the small computed regions go first
     const bool piped = 96 * (inputs ? n : 0) + mbytes >= ((size_t)16 << 20);
@@ -1186,7 +1197,8 @@ int ed_stage(Lane& d, EdBuffers& b, size_t lo, size_t hi, const uint8_t* pk, con
     }
     b.nkeys_distinct = m;
     b.kc_split = kt && kt->kslot && m;
-    b.comb = comb;
+    b.comb = comb && !kt->pass_only;
+    b.comb_pass = comb && kt->pass_only;
     return NWV_OK;
 }
 
@@ -1373,9 +1385,12 @@ int ed_stage_keyed(Lane& d, EdBuffers& b, size_t lo, size_t hi, size_t n_keys, c
     }
     KeyedTail kt{klist.data(), m, koff.data(), ksig.data(), kslot.empty() ? nullptr : kslot.data()};
     // the comb path (k_ed_comb): above TINY_MAX and at most comb_max signatures (0: the caller does
-    // not offer it), every key registered (comb table present), no flag that forces a path
+    // not offer it), every key registered (comb table present), no flag that forces a path.  A
+    // batch past comb_max of at most comb_pass_max signatures (0: off; never a staged batch's)
+    // stages the same tables under the same conditions for k_ed_comb_pass behind its MSM.
     thread_local std::vector<uint32_t> sig_slot, sig_cidx;
-    if (n > (size_t)TINY_MAX && n <= comb_max && !kslot.empty() &&
+    const size_t pass_max = pin_out ? 0 : d.gpu->comb_pass_max.load();
+    if (n > (size_t)TINY_MAX && (n <= comb_max || n <= pass_max) && !kslot.empty() &&
         !(d.flags & (NWV_FLAG_NO_TINY | NWV_FLAG_MSM_ALWAYS | NWV_FLAG_MSM_NEVER))) {
         KeyCache& kc = d.gpu->kc;
         std::lock_guard<std::mutex> g(kc.mu);
@@ -1392,6 +1407,7 @@ int ed_stage_keyed(Lane& d, EdBuffers& b, size_t lo, size_t hi, size_t n_keys, c
         if (all) {
             kt.sig_slot = sig_slot.data();
             kt.sig_cidx = sig_cidx.data();
+            kt.pass_only = n > comb_max;
         }
     }
     rc = ed_stage(d, b, 0, n, pk.data(), sig + 64 * lo, msg_base, msg_off + lo, msg_len + lo, seed32, &kt, dev_msg);
@@ -1438,6 +1454,15 @@ bool verdicts_all_valid(const uint64_t* bits, size_t n) {
 #ifndef NWV_EACH_ROW_MAX_DEFAULT
 #define NWV_EACH_ROW_MAX_DEFAULT 4096
 #endif
+// Largest per-signature pass behind a keyed MSM over registered keys that takes k_ed_comb_pass
+// by default (tools/comb_pass_sweep.py, profiles/comb_pass_sweep.json).  0: opt-in.
+#ifndef NWV_COMB_PASS_MAX_DEFAULT
+#define NWV_COMB_PASS_MAX_DEFAULT 0
+#endif
+// lanes a signature of k_ed_comb_pass (4 or 16): sixteen was the faster form at every swept size
+#ifndef NWV_COMB_PASS_L_DEFAULT
+#define NWV_COMB_PASS_L_DEFAULT 16
+#endif
 
 struct nwv_ctx {
     std::vector<Gpu*> devs;
@@ -1452,6 +1477,9 @@ struct nwv_ctx {
     // per-signature passes of at most each_row_max signatures take k_ed_each_row
     // (nwv_set_each_row_max, same clamp; every device object holds a copy for ed_launch)
     std::atomic<size_t> each_row_max{NWV_EACH_ROW_MAX_DEFAULT};
+    // rejected registered-key batches of at most comb_pass_max signatures name their bad set with
+    // k_ed_comb_pass (nwv_set_comb_pass_max, same clamp; every device object holds a copy)
+    std::atomic<size_t> comb_pass_max{NWV_COMB_PASS_MAX_DEFAULT};
     // the load of every device object, by which calls are placed (place.h; env NWV_PLACE, read at
     // nwv_init); the BLS12-381 engine shares it when it has as many device objects
     std::shared_ptr<nwv::PlaceTable> place;
@@ -1579,6 +1607,7 @@ static int init_devices(nwv_ctx** out, std::vector<int> ordinals, uint32_t flags
         }
     ctx->place.reset(new nwv::PlaceTable(ctx->devs.size(), nwv::place_mode_from_env()));
     (void)nwv_set_each_row_max(ctx, NWV_EACH_ROW_MAX_DEFAULT);
+    (void)nwv_set_comb_pass_max(ctx, NWV_COMB_PASS_MAX_DEFAULT);
     *out = ctx;
     return NWV_OK;
 }
@@ -1673,6 +1702,23 @@ int nwv_diag_each_row(const nwv_ctx* ctx, uint64_t out[2]) {
     for (const Gpu* g : ctx->devs) {
         out[0] += g->n_each_row.load();
         out[1] += g->n_each_row_sigs.load();
+    }
+    return NWV_OK;
+}
+int nwv_set_comb_pass_max(nwv_ctx* ctx, size_t n) {
+    if (!ctx) return set_err(NWV_ERR_ARG, "null context");
+    const size_t v = std::min<size_t>(n, ctx->shard_min - 1);
+    ctx->comb_pass_max = v;
+    for (Gpu* g : ctx->devs) g->comb_pass_max = v;
+    return NWV_OK;
+}
+size_t nwv_comb_pass_max(const nwv_ctx* ctx) { return ctx ? ctx->comb_pass_max.load() : 0; }
+int nwv_diag_comb_pass(const nwv_ctx* ctx, uint64_t out[2]) {
+    if (!ctx || !out) return set_err(NWV_ERR_ARG, "null argument");
+    out[0] = out[1] = 0;
+    for (const Gpu* g : ctx->devs) {
+        out[0] += g->n_comb_pass.load();
+        out[1] += g->n_comb_pass_sigs.load();
     }
     return NWV_OK;
 }
@@ -1946,6 +1992,43 @@ static int comb_on_device(Lane& d, EdBuffers& b, size_t n, hipStream_t stream, i
     return NWV_OK;
 }
 
+// k_ed_comb_pass over a registered-key batch staged for it (b.comb_pass): the per-signature pass
+// of a batch whose MSM did not accept, into the verdict words that batch_on_device reads back
+// (zeroed on the stream first, as ed_launch does for the row kernel).  The tables it reads are
+// held by the call's shared hold of the key cache until the lane goes back.  NWV_COMB_PASS_L
+// (4 or 16): lanes a signature; the default is the faster of the two in tools/comb_pass_sweep.py.
+static int comb_pass_launch(Lane& d, EdBuffers& b, size_t n, hipStream_t stream) {
+    static const int lanes = [] {
+        const char* e = std::getenv("NWV_COMB_PASS_L");
+        const long v = e ? std::strtol(e, nullptr, 10) : 0;
+        return v == 4 || v == 16 ? (int)v : NWV_COMB_PASS_L_DEFAULT;
+    }();
+    const size_t words = (n + 63) / 64;
+    int rc = b.verdict.ensure(8 * words + 8);
+    if (rc) return rc;
+    NWV_HIP(hipMemsetAsync(b.verdict.p, 0, 8 * words, stream));
+    CombPassArgs a{};
+    a.pk = b.pk.as<uint8_t>();
+    a.sig = b.sig.as<uint8_t>();
+    a.msg = b.msg.as<uint8_t>();
+    a.off = b.off.as<uint64_t>();
+    a.len = b.len.as<uint32_t>();
+    a.kc = d.gpu->kc.recs.as<uint32_t>();
+    a.combs = d.gpu->kc.combs.as<uint32_t>();
+    a.bcomb = d.gpu->comb.as<uint32_t>();
+    a.kslot = b.comb_slot.as<uint32_t>();
+    a.cidx = b.comb_cidx.as<uint32_t>();
+    a.verdict = b.verdict.as<unsigned long long>();
+    a.n = (uint32_t)n;
+    const dim3 grid((unsigned)((n + COMB_PASS_G - 1) / COMB_PASS_G));
+    if (lanes == 4) hipLaunchKernelGGL(k_ed_comb_pass4, grid, dim3(64 * CombPassShape<4>::WAVES), 0, stream, a);
+    else hipLaunchKernelGGL(k_ed_comb_pass16, grid, dim3(64 * CombPassShape<16>::WAVES), 0, stream, a);
+    NWV_HIP(hipGetLastError());
+    d.gpu->n_comb_pass++;
+    d.gpu->n_comb_pass_sigs += n;
+    return NWV_OK;
+}
+
 // Batch verdict of resident buffers: MSM, then (only if it rejects) the per-signature fallback
 // for the exact bad set.  bits: the shard's verdict words (may be null).  A tiny keyed batch by
 // registered keys takes the one-launch per-signature path instead (exact bits, no fallback), and
@@ -2048,7 +2131,13 @@ static int batch_on_device(Lane& d, EdBuffers& b, size_t n, const uint8_t seed[3
     }
     htrace("batch:fallback");
     d.gpu->n_each++;
-    if ((rc = ed_launch(d, b, n, stream, nullptr, msm_reusable(d, b, use_msm)))) return rc;
+    // a batch staged for it (b.comb_pass: registered keys, under the call's hold of the key cache)
+    // names its bad set from the key combs instead of a Straus chain a signature
+    if (b.comb_pass) {
+        if ((rc = comb_pass_launch(d, b, n, stream))) return rc;
+    } else if ((rc = ed_launch(d, b, n, stream, nullptr, msm_reusable(d, b, use_msm)))) {
+        return rc;
+    }
     std::vector<uint64_t> tmp;
     uint64_t* out = bits;
     if (!out) {

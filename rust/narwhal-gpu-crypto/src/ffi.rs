@@ -189,6 +189,9 @@ extern "C" {
     pub fn nwv_each_row_max(ctx: *const NwvCtx) -> usize;
     pub fn nwv_diag_each_row(ctx: *const NwvCtx, out: *mut u64) -> c_int;
     pub fn nwv_diag_each_row_reuse(ctx: *const NwvCtx, out: *mut u64) -> c_int;
+    pub fn nwv_set_comb_pass_max(ctx: *mut NwvCtx, n: usize) -> c_int;
+    pub fn nwv_comb_pass_max(ctx: *const NwvCtx) -> usize;
+    pub fn nwv_diag_comb_pass(ctx: *const NwvCtx, out: *mut u64) -> c_int;
     pub fn nwv_device_ordinal(ctx: *const NwvCtx, i: c_int) -> c_int;
     pub fn nwv_diag_device_counters(
         ctx: *mut NwvCtx,
