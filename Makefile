@@ -45,7 +45,8 @@ hostemu: tests/_build/libhostemu.so tests/_build/libsvcstub.so tests/_build/libb
 	tests/_build/libplace.so tests/_build/libkcalloc.so tests/_build/libgroupkeys.so tests/_build/libeachemu.so \
 	tests/_build/libblswbemu.so tests/_build/libblsmsgring.so tests/_build/libblsmremu.so \
 	tests/_build/libblsapkring.so tests/_build/libblsaremu.so tests/_build/libblskeybatch.so \
-	tests/_build/libblskbemu.so tests/_build/libblswvemu.so tests/_build/libcombpassemu.so
+	tests/_build/libblskbemu.so tests/_build/libblswvemu.so tests/_build/libcombpassemu.so \
+	tests/_build/libtailrcemu.so
 # the wave interpreter one program at a time with its limb bounds evaluated (BLS_BOUNDS_CHECK;
 # tests/test_bls_wave_vectors_hostemu.py)
 tests/_build/libblswvemu.so: tests/hostemu/bls_wave_vectors_hostemu.cpp $(BLS_SRC) $(BLS_SHARED)
@@ -141,6 +142,10 @@ tests/_build/libfeseeded.so: tests/hostemu/fe_seeded_hostemu.cpp narwhal_amd/csr
 tests/_build/libtrimemu.so: tests/hostemu/trim_hostemu.cpp $(CSRC)
 	@mkdir -p tests/_build
 	$(HIPCC) -std=c++17 -O1 --offload-host-only -x hip -DNWV_BOUNDS_CHECK -fPIC -shared -o $@ tests/hostemu/trim_hostemu.cpp
+# the tail's chunk planes by rows and columns on the host (tests/test_tail_rc_hostemu.py)
+tests/_build/libtailrcemu.so: tests/hostemu/tail_rc_hostemu.cpp $(CSRC)
+	@mkdir -p tests/_build
+	$(HIPCC) -std=c++17 -O1 --offload-host-only -x hip -DNWV_BOUNDS_CHECK -fPIC -shared -o $@ tests/hostemu/tail_rc_hostemu.cpp
 # the reduction mod l by folding, the unreduced sums of z s, the in-order digit recoding and the
 # decompression with its stash on the host (tests/test_fold_hostemu.py)
 tests/_build/libfoldemu.so: tests/hostemu/fold_hostemu.cpp $(CSRC)

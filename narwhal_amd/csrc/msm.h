@@ -458,4 +458,89 @@ NWV_HD void msm_segment_sums(int L, LoadBucket load_bucket, ge_p3& run, ge_p3& a
     }
 }
 
+// Entries per bucket lane (T of k_msm_bucket[_q]; msm_plan).  About two waves per SIMD of bucket
+// lanes (256 CUs x 4 SIMDs x 2 x 64), 8..64 entries each.  Tiny batches (a certificate's few
+// signatures): nearly every bucket is empty, and each lane's segment close walks to the next
+// non-empty bucket by dependent loads; two entries a lane (C1 Certificate::verify n = 4: p50
+// 0.191 -> 0.184 ms; a 1K batch is slower below 8).
+// Large batches of the lane kernel (more than 4,096 signatures on the chunked sort, and more
+// entries than the floor of 8 serves at two waves per SIMD): ONE wave per SIMD instead.  Every
+// bucket lane after a bucket's first hands the tail a continuation piece (a 160-byte record
+// stored, reloaded and joined by a 9-multiply addition), so half the lanes are half the pieces;
+// with batches in flight the step follows the instruction count, and at 65,536 signatures the
+// lone batch's k_msm_bucket + k_msm_tail stay inside the two-wave plan's range up to here:
+// 30 entries a lane, while 31, 32 and 40 leave it, the bucket kernel growing faster than the
+// tail shrinks (profiles/with_window_rowcol_msm_seg_sweep_n65536.json).  The bucket kernel
+// itself issues 1.6 % more (each lane's first entry is a cheap seed, and there are half as
+// many first entries); the tail saves three times that.
+NWV_HD uint32_t msm_bucket_seg(uint64_t n, uint64_t entries, uint32_t chunks) {
+    const uint64_t two_waves = 256 * 4 * 2 * 64;
+    uint64_t seg = entries / two_waves;
+    seg = seg < 8 ? 8 : seg > 64 ? 64 : seg;
+    if (entries <= 2048) seg = 2;
+    if (n > 4096 && chunks > 1 && entries / two_waves > 8) {
+        seg = entries / (two_waves / 2);
+        if (seg > 64) seg = 64;
+    }
+    return (uint32_t)seg;
+}
+
+// Bit planes of a chunk of C = 2^m bucket sums by rows and columns (k_msm_tail, C > 128).  The
+// chunk is viewed as 2^lr rows x 2^lc columns, lc = m / 2, lr = m - lc, bucket t = r 2^lc + c.  Bit
+// k of t is bit k of c (k < lc) or bit k - lc of r, so the planes k < lc are the planes of the
+// column sums H_c and the planes k >= lc those of the row sums G_r: two pairwise trees (C - 2^lr
+// and C - 2^lc additions) and two small bit-plane butterflies (lc 2^(lc-1) and lr 2^(lr-1)) instead
+// of one butterfly of m C / 2 additions, 544 against 1,024 at C = 256, in the same m levels.
+//
+// Slots: the C raw sums sit in slots 0 .. C-1.  The row chain works in place on the even slots it
+// leaves itself (tree level j: slot g 2^(j+1) += slot g 2^(j+1) + 2^j; then G_r in slot r 2^lc).
+// The column chain's first level reads the raw sums i and i + C / 2 and writes H's partial sum i
+// into the ODD slot 2 i + 1, which the row chain never reads after its own first level; from
+// there on it stays on odd slots.  So phase 0 must read every operand before any result is
+// stored (the caller puts a barrier between), and the later phases of the two chains are disjoint.
+// Phase ph < m: operation g of the phase, row chain first (tree level ph while ph < lc, then the
+// butterfly of the G_r), then the column chain (tree level ph while ph < lr, then the butterfly
+// of the H_c; none when lc = 0).  At most C operations a phase (phase 0), halving to 2^(lr-1) +
+// 2^(lc-1): at C = 256, 4 + 2 + 1 + 1 + 4 x 1 = 12 waves of additions against 8 x 2.
+struct TailRcOp {
+    int d, a, b;  // slot d = slot a + slot b
+};
+NWV_HD bool tail_rc_op(int m, int ph, int g, TailRcOp& op) {
+    const int lc = m >> 1, lr = m - lc, C = 1 << m;
+    const int nrow = ph < lc ? C >> (ph + 1) : 1 << (lr - 1);
+    if (g < nrow) {
+        if (ph < lc) {
+            op.d = op.a = g << (ph + 1);
+            op.b = op.d + (1 << ph);
+        } else {
+            const int k = ph - lc, o = 1 << k, r = ((g >> k) << (k + 1)) | (g & (o - 1));
+            op.d = op.a = r << lc;
+            op.b = (r + o) << lc;
+        }
+        return true;
+    }
+    if (lc == 0) return false;
+    g -= nrow;
+    const int ncol = ph < lr ? C >> (ph + 1) : 1 << (lc - 1);
+    if (g >= ncol) return false;
+    if (ph == 0) {
+        op.d = 2 * g + 1;
+        op.a = g;
+        op.b = g + (C >> 1);
+    } else if (ph < lr) {
+        op.d = op.a = 2 * g + 1;
+        op.b = 2 * (g + ncol) + 1;
+    } else {
+        const int k = ph - lr, o = 1 << k, c = ((g >> k) << (k + 1)) | (g & (o - 1));
+        op.d = op.a = 2 * c + 1;
+        op.b = 2 * (c + o) + 1;
+    }
+    return true;
+}
+// after the m phases: the slot of plane k < m, or of the chunk's sum (k = m)
+NWV_HD int tail_rc_plane_slot(int m, int k) {
+    if (k >= m) return 0;
+    return k < (m >> 1) ? 2 * (1 << k) + 1 : 1 << k;
+}
+
 }  // namespace nwv

@@ -1016,6 +1016,9 @@ struct MsmTailArgs {
     // many buckets on quads whatever quad_max_c says: one quad pass a level at C = 128
     uint32_t quad_top_c;
     uint32_t hseq;
+    // lane-local chunks of at least this many buckets get their planes by rows and columns
+    // (msm.h tail_rc_op) instead of one butterfly: 256, where that saves waves of additions
+    uint32_t rc_min_c;
 };
 // bound on the final-sum wave's polls of one window's ready flag (each a coherent load plus a
 // short sleep; seconds in all).  Reaching it ends the kernel with *verdict = 2, "undetermined":
@@ -1222,11 +1225,31 @@ __device__ __forceinline__ bool msm_tail_window(const MsmLayout& lay, const MsmT
             __syncthreads();
         }
         if (t < C) p = load_p3(mine);
+    } else if ((uint32_t)C >= a.rc_min_c) {
+        // rows and columns (msm.h tail_rc_op): row and column sums by pairwise trees, then the
+        // planes from two small butterflies, both chains side by side in the same lgC levels.
+        // The operations of a level are packed onto the first lanes, so a level costs
+        // ceil(ops / 64) waves of additions: 12 a chunk at C = 256 against the butterfly's 16.
+        // Level 0 reads every raw sum before any result lands (the column chain's first results
+        // go to the odd slots, whose raw sums the row chain reads at this level only).
+        if (t < C) store_p3(mine, p);
+        __syncthreads();
+        for (int ph = 0; ph < lgC; ph++) {
+            TailRcOp op;
+            const bool on = tail_rc_op(lgC, ph, t, op);
+            ge_p3 r = p;
+            if (on) r = p3_add(load_p3(lds + P3_WORDS * op.a), load_p3(lds + P3_WORDS * op.b));
+            if (ph == 0) __syncthreads();
+            if (on) store_p3(lds + P3_WORDS * op.d, r);
+            __syncthreads();
+        }
+        if (t < C && !(t & (t - 1)))  // lane 0: R_s; lane 2^k: plane k
+            p = load_p3(lds + P3_WORDS * tail_rc_plane_slot(lgC, t ? tail_lg(t) : lgC));
     } else {
-        // lane-local additions in LDS: every level's C / 2 additions on the first C / 2 lanes
-        // (lane g adds slot i + o into slot i, i = g with a zero inserted at bit lg), so only
-        // ceil(C / 128) waves of the workgroup issue them (round 4: every lane with bit o clear,
-        // i.e. all four waves for o < 64, half of each idle)
+        // one bit-plane butterfly (C <= 128: its lgC levels take one wave of additions each,
+        // which rows and columns cannot beat).  Lane-local additions in LDS: every level's C / 2
+        // additions on the first C / 2 lanes (lane g adds slot i + o into slot i, i = g with a
+        // zero inserted at bit lg), so only ceil(C / 128) waves of the workgroup issue them
         if (t < C) store_p3(mine, p);
         __syncthreads();
         for (int o = 1, lg = 0; o < C; o <<= 1, lg++) {

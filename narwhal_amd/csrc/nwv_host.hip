@@ -651,12 +651,7 @@ MsmPlan msm_plan(size_t n, size_t na, bool split = false, int sort2 = 0) {
         }
     }
     p.max_entries = (uint64_t)(na + 1) * p.lay.nw + (uint64_t)n * p.lay.nw_z;
-    // ~2 waves per SIMD of bucket lanes (256 CUs x 4 SIMDs x 2 x 64), 8..64 entries each
-    p.seg = (uint32_t)std::min<uint64_t>(64, std::max<uint64_t>(8, p.max_entries / (256 * 4 * 2 * 64)));
-    // tiny batches (a certificate's few signatures): nearly every bucket is empty, and each lane's
-    // segment close walks to the next non-empty bucket by dependent loads; two entries a lane
-    // (C1 Certificate::verify n = 4: p50 0.191 -> 0.184 ms; a 1K batch is slower below 8)
-    if (p.max_entries <= 2048) p.seg = 2;
+    p.seg = msm_bucket_seg(n, p.max_entries, p.chunks);  // (msm.h)
     if (const char* e = std::getenv("NWV_MSM_SEG")) p.seg = (uint32_t)std::max(1L, std::strtol(e, nullptr, 10));
     p.nseg = (p.max_entries + p.seg - 1) / p.seg;
     // tail: chunks of at most 256 buckets (one per lane of a k_msm_tail workgroup)
@@ -877,6 +872,12 @@ int msm_launch(Lane& d, EdBuffers& b, size_t n, const uint8_t seed32[32], hipStr
         const char* e = std::getenv("NWV_TAIL_QUAD_TOP_C");
         return e ? (uint32_t)std::strtoul(e, nullptr, 10) : 128u;
     }();
+    // lane-local chunk planes by rows and columns from this chunk size on (NWV_TAIL_RC_MIN_C: 2 puts
+    // every lane-local chunk on that form, above 256 none)
+    static const uint32_t rc_min_c = [] {
+        const char* e = std::getenv("NWV_TAIL_RC_MIN_C");
+        return e ? (uint32_t)std::max(2UL, std::strtoul(e, nullptr, 10)) : 256u;
+    }();
     // NWV_TAIL_SPIN_LIMIT (test hook): the _spin1 kernels, whose final-sum wave gives up on a window
     // at its first poll -- the undetermined outcome
     static const bool spin1 = std::getenv("NWV_TAIL_SPIN_LIMIT") != nullptr;
@@ -884,7 +885,7 @@ int msm_launch(Lane& d, EdBuffers& b, size_t n, const uint8_t seed32[32], hipStr
                          b.m_tpart.as<uint32_t>(), b.m_wsum.as<uint32_t>(),
                          b.m_ctr.as<uint32_t>(), state, b.m_partial.as<uint32_t>(),
                          d.gpu->comb.as<uint32_t>(), sblk, quad_max_c, state + 1, state + 2, p.tail_S, st_buf,
-                         hverdict, quad_top_c, hseq & 0x3FFFFFFFu};
+                         hverdict, quad_top_c, hseq & 0x3FFFFFFFu, rc_min_c};
     // combine items per thread: (lg C + 1) x S_w over the windows (C = nb / S_w buckets per chunk)
     int items = 0;
     for (int w = 0; w < p.lay.nw; w++) {
