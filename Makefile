@@ -9,7 +9,7 @@ BLS_SRC := narwhal_amd/csrc/nwv_bls.hip narwhal_amd/csrc/bls381.h narwhal_amd/cs
 	narwhal_amd/csrc/bls_wave_prog.h narwhal_amd/csrc/bls_shard.h narwhal_amd/csrc/bls_msg_ring.h \
 	narwhal_amd/csrc/bls_apk_ring.h narwhal_amd/csrc/bls_key_batch.h include/nwv_bls.h
 # headers that both engines' translation units include (they stay in CSRC)
-BLS_SHARED := narwhal_amd/csrc/shard.h narwhal_amd/csrc/place.h
+BLS_SHARED := narwhal_amd/csrc/shard.h narwhal_amd/csrc/place.h narwhal_amd/csrc/lane_pool.h narwhal_amd/csrc/lane_stream.h
 CSRC := $(filter-out $(BLS_SRC),$(wildcard narwhal_amd/csrc/*.h narwhal_amd/csrc/*.hip narwhal_amd/csrc/*.cpp)) \
 	include/nwv.h include/nwv_types.h include/nwv_service.h
 
@@ -46,7 +46,7 @@ hostemu: tests/_build/libhostemu.so tests/_build/libsvcstub.so tests/_build/libb
 	tests/_build/libblswbemu.so tests/_build/libblsmsgring.so tests/_build/libblsmremu.so \
 	tests/_build/libblsapkring.so tests/_build/libblsaremu.so tests/_build/libblskeybatch.so \
 	tests/_build/libblskbemu.so tests/_build/libblswvemu.so tests/_build/libcombpassemu.so \
-	tests/_build/libtailrcemu.so
+	tests/_build/libtailrcemu.so tests/_build/liblanepool.so
 # the wave interpreter one program at a time with its limb bounds evaluated (BLS_BOUNDS_CHECK;
 # tests/test_bls_wave_vectors_hostemu.py)
 tests/_build/libblswvemu.so: tests/hostemu/bls_wave_vectors_hostemu.cpp $(BLS_SRC) $(BLS_SHARED)
@@ -92,6 +92,10 @@ tests/_build/libkcalloc.so: tests/hostemu/keycache_alloc_stub.cpp narwhal_amd/cs
 tests/_build/libplace.so: tests/hostemu/place_stub.cpp narwhal_amd/csrc/place.h
 	@mkdir -p tests/_build
 	g++ -O1 -g -std=c++17 -fPIC -shared -pthread -o $@ tests/hostemu/place_stub.cpp
+# the lane pools' lease rule (lane_pool.h) with no HIP (tests/test_lane_pool_host.py)
+tests/_build/liblanepool.so: tests/hostemu/lane_pool_stub.cpp narwhal_amd/csrc/lane_pool.h
+	@mkdir -p tests/_build
+	g++ -O1 -g -std=c++17 -fPIC -shared -pthread -o $@ tests/hostemu/lane_pool_stub.cpp
 # the BLS and Ed25519 calls' split over a multi-device context (bls_shard.h, shard.h) with stub per-device work
 tests/_build/libblsshard.so: tests/hostemu/bls_shard_stub.cpp narwhal_amd/csrc/bls_shard.h narwhal_amd/csrc/shard.h
 	@mkdir -p tests/_build

@@ -183,6 +183,40 @@ int nwv_device_ordinal(const nwv_ctx* ctx, int i);
  * [0] and [1] count the engine's own calls; [2] and [3] are the device's load, which both engines
  * share when they have the same number of device objects. */
 int nwv_diag_device_counters(nwv_ctx* ctx, int engine, int device_index, uint64_t* out, int cap);
+/* Latency class (opt-in; 0 = off, the default).  Every call leases a lane -- a stream with its
+ * staging and scratch buffers -- of its device object for its whole duration, and waits when all
+ * are out.  With a bound n > 0 for an engine, that engine's calls of at most n items are latency
+ * class: they take, in order, an idle reserved lane, a new reserved lane (each device object opens
+ * up to NWV_LATENCY_LANES of them on demand: env, read at nwv_init, default 2, 1..4), an idle
+ * ordinary lane, a new ordinary lane, and otherwise wait for the first lane of either pool.  Every
+ * stream of a reserved lane is non-blocking at the greatest priority the device reports (default
+ * priority where it reports no range).  All other calls lease from the ordinary lanes only, as
+ * without the bound.
+ *   NWV_ENGINE_ED25519: signature calls that are one range, n = signatures (verify_each,
+ *     verify_batch[_keyed|_grouped], pubkey_verify, the trait surface, the fused
+ *     verify_batch_keyed_digests; the types layer and the service through them); digest calls
+ *     (nwv_blake2b256_many, nwv_batch_digest_serialized) of at most n messages and at most
+ *     NWV_LATENCY_DIGEST_BYTES input bytes in total (env, read at nwv_init, default 1 MiB)
+ *   NWV_ENGINE_BLS: nwv_bls_verify_many[_ahead] and nwv_bls_aggregate of at most n items (the
+ *     trait surface, the BLS types layer and service through them)
+ * Always ordinary: calls that split over devices, nwv_stage_* and staged runs, key-cache
+ * registration and retain, signing, key generation, the hash and pairing primitives.
+ * Values at or above the engine's shard minimum are clamped to just below it (a latency-class call
+ * is always a single range); the getter returns the value in force.  A new value applies to later
+ * leases; lanes are never destroyed before nwv_free.  With the bound at 0 no reserved lane and no
+ * priority stream is ever created. */
+int nwv_set_latency_max(nwv_ctx* ctx, int engine, size_t n);
+size_t nwv_latency_max(const nwv_ctx* ctx, int engine);
+/* Lane counters of one device object: writes min(cap, count) values, returns count.
+ * [0] latency-class calls   [1] of those, the calls that leased a reserved lane
+ * [2] of those, the calls that had to wait for any lane
+ * [3] all other calls   [4] of those, the calls that waited
+ * [5] reserved lanes open   [6] reserved-lane cap   [7] ordinary lanes open */
+int nwv_diag_qos(nwv_ctx* ctx, int engine, int device_index, uint64_t* out, int cap);
+/* out[0] priority of the reserved lanes' streams, as the runtime reports it for a reserved lane's
+ * main stream (0 if none is open yet); out[1] the device's greatest and out[2] its least priority,
+ * from the runtime's priority-range query */
+int nwv_diag_qos_priority(nwv_ctx* ctx, int engine, int device_index, int out[3]);
 int nwv_abi_version(void);
 /* last error text for this thread (static storage, never NULL) */
 const char* nwv_last_error(void);

@@ -117,7 +117,8 @@ def load():
         f = getattr(lib, name)
         f.argtypes = args
         f.restype = res
-    # the aggregate-key ring's entry points (narwhal_amd.bls wraps them) and the comb pass's; an
+    # the aggregate-key ring's entry points (narwhal_amd.bls wraps them), the comb pass's and the
+    # latency class's; an
     # older build selected with NWV_LIB for an A/B run lacks them, and calling one there still raises
     newer = {
         "nwv_set_comb_pass_max": ([_vp, _sz], _i32),
@@ -127,6 +128,11 @@ def load():
         "nwv_bls_apk_ring": ([_vp], _sz),
         "nwv_bls_last_apk": ([_vp, _vp], _i32),
         "nwv_bls_apk_ring_stats": ([_vp, _vp], _i32),
+        # the latency class (Engine.set_latency_max, diag_qos)
+        "nwv_set_latency_max": ([_vp, _i32, _sz], _i32),
+        "nwv_latency_max": ([_vp, _i32], _sz),
+        "nwv_diag_qos": ([_vp, _i32, _i32, _vp, _i32], _i32),
+        "nwv_diag_qos_priority": ([_vp, _i32, _i32, _vp], _i32),
     }
     for name, (args, res) in newer.items():
         f = getattr(lib, name, None)
@@ -266,6 +272,34 @@ class Engine:
         if k < 6:
             _check(k if k < 0 else NWV_ERR_ARG)
         return {nm: int(v) for nm, v in zip(names[:k], out)}
+
+    def set_latency_max(self, engine, n):
+        """nwv_set_latency_max: calls of an engine (0: Ed25519 and digests, 1: BLS12-381) of at most n
+        items lease from the device's reserved, high-priority lanes (0: off, the default)"""
+        _check(self.lib.nwv_set_latency_max(self._h, int(engine), int(n)))
+
+    def latency_max(self, engine):
+        """nwv_latency_max: the bound in force for an engine"""
+        return int(self.lib.nwv_latency_max(self._h, int(engine)))
+
+    def diag_qos(self, engine, device_index=0):
+        """nwv_diag_qos: the lane counters of one device object of an engine: {'latency_calls',
+        'latency_reserved', 'latency_waited', 'other_calls', 'other_waited', 'reserved_open',
+        'reserved_cap', 'ordinary_open'}"""
+        names = ("latency_calls", "latency_reserved", "latency_waited", "other_calls", "other_waited",
+                 "reserved_open", "reserved_cap", "ordinary_open")
+        out = np.zeros(len(names), dtype=np.uint64)
+        k = self.lib.nwv_diag_qos(self._h, int(engine), int(device_index), out.ctypes.data, len(names))
+        if k < len(names):
+            _check(k if k < 0 else NWV_ERR_ARG)
+        return {nm: int(v) for nm, v in zip(names, out)}
+
+    def diag_qos_priority(self, engine, device_index=0):
+        """nwv_diag_qos_priority: (priority of a reserved lane's main stream, 0 if none is open; the
+        device's greatest priority; its least priority)"""
+        out = np.zeros(3, dtype=np.int32)
+        _check(self.lib.nwv_diag_qos_priority(self._h, int(engine), int(device_index), out.ctypes.data))
+        return int(out[0]), int(out[1]), int(out[2])
 
     def set_comb_batch_max(self, n):
         """nwv_set_comb_batch_max: the largest registered-key batch that takes the comb path (0: off)"""

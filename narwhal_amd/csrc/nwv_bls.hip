@@ -39,6 +39,8 @@
 #include "bls_msg_ring.h"
 #include "bls_apk_ring.h"
 #include "bls_key_batch.h"
+#include "lane_pool.h"
+#include "lane_stream.h"
 #include "place.h"
 #include "stage_args.h"
 
@@ -1243,6 +1245,7 @@ struct BlsKeyCache {
 struct BlsLane {
     hipStream_t stream = nullptr;              // H2D, signatures, pairing check, D2H
     hipStream_t side[2] = {nullptr, nullptr};  // keys + key sums (+ hash to G1 on small wave calls); hash to G1
+    bool high = false;  // a reserved lane (lane_pool.h): its streams, side[1] included, at the greatest priority
     HBuf stage;
     DBuf in, work;
     // the key-transposed batch check's own buffers (sized by the plan, made after the pre-pairing
@@ -1253,7 +1256,7 @@ struct BlsLane {
     // [0,1] keys, [1,2] key sums (side 0); [3,4] signatures (main); [5,6] hash to G1 (side 1; side
     // 0 on small wave calls); [7,8] pairing check (main); [9] inputs resident, [10] side 0 done,
     // [11] side 1 done.  side[1] is created by the first call that needs it: a lane of small wave
-    // calls holds two streams, so eight lanes map one to one onto 16 hardware queues
+    // calls holds two streams, so the eight ordinary lanes map one to one onto 16 hardware queues
     hipEvent_t ev[12] = {};
     // ordering only (no timestamps): [0] inputs resident, [1] signatures decoded (small wave calls),
     // [2] key sums done (small wave calls that fill aggregate-key ring slots)
@@ -1298,7 +1301,8 @@ struct BlsSigCache {
     std::vector<uint8_t> held;  // slot s is mapped
     std::vector<uint8_t> busy;  // reserved by a call still in flight
     uint32_t next = 0;
-    // n free slots from the ring's cursor (busy ones skipped: at most kMaxLanes x 1,024 are),
+    // n free slots from the ring's cursor (busy ones skipped: at most kMaxBusySlots are, one
+    // keeping call of up to 1,024 items on each of a device's lanes, reserved ones included),
     // unmapped and marked busy -> out
     int reserve(size_t n, std::vector<uint32_t>& out) {
         std::unique_lock<std::shared_mutex> lk(mu);
@@ -1360,7 +1364,11 @@ struct SigSlots {
     }
 };
 
-constexpr size_t kMaxLanes = 8;
+constexpr size_t kMaxLanes = 8;  // ordinary lanes of a device; up to LATENCY_LANES_MAX reserved ones beside them
+// the verified-signature ring's busy slots at any moment: every lane, ordinary or reserved, runs at
+// most one call, and a call that keeps its signatures has at most 1,024 items (verify_on)
+constexpr size_t kMaxBusySlots = (kMaxLanes + nwv::LATENCY_LANES_MAX) * 1024;
+static_assert(kMaxBusySlots + 1024 <= SC_CAP, "a keeping call always finds 1,024 free ring slots");
 
 // The hashed message points of a device (nwv_bls_set_msg_ring; bls_msg_ring.h keeps the books).
 // Small wave calls look their messages up, pin the hits and reserve a slot per distinct miss
@@ -1469,10 +1477,15 @@ struct BlsDev {
     BlsSigCache sc;
     BlsMsgCache mr;
     BlsApkCache ar;
-    std::mutex pool_mu;
-    std::condition_variable pool_cv;
-    std::vector<std::unique_ptr<BlsLane>> lanes;
-    std::vector<BlsLane*> idle;
+    // the lanes: kMaxLanes ordinary ones, and NWV_LATENCY_LANES reserved ones for calls of at most
+    // latency_max items (nwv_set_latency_max; 0: no call is latency class), lane_pool.h
+    nwv::LanePool<BlsLane> pool;
+    std::atomic<size_t> latency_max{0};
+    bool latency_priority = true;  // (env NWV_LATENCY_PRIORITY=0: reserved lanes at default priority)
+    BlsDev() { pool.set_caps(kMaxLanes, nwv::latency_lanes_from_env()); }
+    ~BlsDev() {
+        for (BlsLane* l : pool.all()) delete l;
+    }
     std::mutex stat_mu;  // the last completed verify_many call's stage times and path
     double last_ms[5] = {0, 0, 0, 0, 0};
     int last_path = 0;
@@ -1526,6 +1539,7 @@ int ctx_of(nwv_ctx* ctx, BlsCtx** out) {
             auto* d = new BlsDev;
             d->ordinal = nwv_internal_hip_device(ctx, k);
             d->flags = nwv_internal_ctx_flags(ctx);
+            d->latency_priority = nwv::latency_priority_from_env();
             c->devs.push_back(d);
         }
     nwv::PlaceTable* shared = nwv_internal_place(ctx);
@@ -1578,48 +1592,35 @@ int on_all_devices(BlsCtx& c, Fn fn) {
     return rc;
 }
 
-// a lane of the device's pool for the duration of one call (created on demand, at most kMaxLanes)
+// a lane of the device's pool for the duration of one call, by the rule of lane_pool.h (created on
+// demand: at most kMaxLanes ordinary lanes, and the reserved ones that only latency-class calls take)
 class LaneLease {
   public:
-    explicit LaneLease(BlsDev& d) : d_(d) {
-        std::unique_lock<std::mutex> g(d.pool_mu);
-        for (;;) {
-            if (!d.idle.empty()) {
-                lane_ = d.idle.back();
-                d.idle.pop_back();
-                break;
+    explicit LaneLease(BlsDev& d, bool latency = false) : d_(d) {
+        lane_ = d.pool.lease(latency, [&](bool reserved) -> BlsLane* {
+            auto l = std::make_unique<BlsLane>();
+            l->high = reserved && d.latency_priority;
+            if (hipSetDevice(d.ordinal) != hipSuccess || nwv::lane_stream_create(&l->stream, l->high) != hipSuccess ||
+                nwv::lane_stream_create(&l->side[0], l->high) != hipSuccess) {
+                rc_ = nwv_internal_set_err(NWV_ERR_HIP, "bls stream");
+                return nullptr;
             }
-            if (d.lanes.size() < kMaxLanes) {
-                auto l = std::make_unique<BlsLane>();
-                if (hipSetDevice(d.ordinal) != hipSuccess ||
-                    hipStreamCreateWithFlags(&l->stream, hipStreamNonBlocking) != hipSuccess ||
-                    hipStreamCreateWithFlags(&l->side[0], hipStreamNonBlocking) != hipSuccess) {
-                    rc_ = nwv_internal_set_err(NWV_ERR_HIP, "bls stream");
-                    return;
+            for (auto& e : l->ev)
+                if (hipEventCreate(&e) != hipSuccess) {
+                    rc_ = nwv_internal_set_err(NWV_ERR_HIP, "bls event");
+                    return nullptr;
                 }
-                for (auto& e : l->ev)
-                    if (hipEventCreate(&e) != hipSuccess) {
-                        rc_ = nwv_internal_set_err(NWV_ERR_HIP, "bls event");
-                        return;
-                    }
-                for (auto& e : l->sev)
-                    if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) {
-                        rc_ = nwv_internal_set_err(NWV_ERR_HIP, "bls event");
-                        return;
-                    }
-                lane_ = l.get();
-                d.lanes.push_back(std::move(l));
-                break;
-            }
-            d.pool_cv.wait(g);
-        }
-        if (hipSetDevice(d.ordinal) != hipSuccess) rc_ = nwv_internal_set_err(NWV_ERR_HIP, "hipSetDevice (bls)");
+            for (auto& e : l->sev)
+                if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) {
+                    rc_ = nwv_internal_set_err(NWV_ERR_HIP, "bls event");
+                    return nullptr;
+                }
+            return l.release();
+        });
+        if (lane_ && hipSetDevice(d.ordinal) != hipSuccess) rc_ = nwv_internal_set_err(NWV_ERR_HIP, "hipSetDevice (bls)");
     }
     ~LaneLease() {
-        if (!lane_) return;
-        std::lock_guard<std::mutex> g(d_.pool_mu);
-        d_.idle.push_back(lane_);
-        d_.pool_cv.notify_one();
+        if (lane_) d_.pool.give_back(lane_);
     }
     int rc() const { return rc_; }
     BlsLane& operator*() { return *lane_; }
@@ -1752,8 +1753,9 @@ int keycache_register(BlsDev& d, size_t n_keys, const uint8_t* keys) {
 int verify_on(BlsDev& d, size_t n_keys, const uint8_t* keys, size_t n, const uint8_t* sigs, const uint32_t* pk_off,
               const uint32_t* pk_cnt, const uint32_t* pk_idx, size_t n_idx, const uint8_t* msg_base,
               const uint64_t* msg_off, const uint32_t* msg_len, size_t msg_bytes, const uint8_t* dst, size_t dl,
-              int32_t* status, const Ahead* ahead = nullptr, uint64_t* mstat = nullptr, uint64_t* astat = nullptr) {
-    LaneLease lane(d);
+              int32_t* status, const Ahead* ahead = nullptr, uint64_t* mstat = nullptr, uint64_t* astat = nullptr,
+              bool latency = false) {
+    LaneLease lane(d, latency);
     if (lane.rc()) return lane.rc();
     BlsLane& L = *lane;
     static const uint8_t zero[8] = {0};
@@ -1837,7 +1839,8 @@ int verify_on(BlsDev& d, size_t n_keys, const uint8_t* keys, size_t n, const uin
     }
     const size_t n_dec = fill_slot.size();  // keys decoded by this call
     // verified signatures stay decoded in the device's ring (BlsSigCache) for aggregates
-    // (n <= 1,024 whatever NWV_BLS_WAVE_MAX says: kMaxLanes calls hold at most 8,192 busy slots)
+    // (n <= 1,024 whatever NWV_BLS_WAVE_MAX says: the calls in flight on a device's lanes then hold
+    // at most kMaxBusySlots busy slots)
     const bool keep = wave_small && n <= 1024 && !(d.flags & NWV_FLAG_NO_SIGCACHE);
     SigSlots kept;
     if (keep) {
@@ -2163,7 +2166,7 @@ int verify_on(BlsDev& d, size_t n_keys, const uint8_t* keys, size_t n, const uin
             for (int k = 0; k < 4; k++) astat[k] += acount[k];
         return finish(3);
     }
-    if (!L.side[1] && hipStreamCreateWithFlags(&L.side[1], hipStreamNonBlocking) != hipSuccess)
+    if (!L.side[1] && nwv::lane_stream_create(&L.side[1], L.high) != hipSuccess)
         return nwv_internal_set_err(NWV_ERR_HIP, "bls stream");
     s2 = L.side[1];
     BLS_HIP(hipStreamWaitEvent(s2, L.sev[0], 0));
@@ -2522,6 +2525,16 @@ int msg_ring_fill(BlsDev& d, size_t n, const uint8_t* base, const uint64_t* off,
     return NWV_OK;
 }
 
+// a call splits over the devices only into ranges of at least this many items (env
+// NWV_BLS_SHARD_MIN, read once)
+size_t bls_shard_min() {
+    static const size_t v = [] {
+        const char* e = std::getenv("NWV_BLS_SHARD_MIN");
+        return e ? (size_t)std::strtoull(e, nullptr, 10) : (size_t)256;
+    }();
+    return v;
+}
+
 const uint8_t* dst_or_default(const uint8_t* dst, size_t* dl) {
     if (dst) return dst;
     *dl = sizeof(NWV_BLS_DST) - 1;
@@ -2555,6 +2568,44 @@ __attribute__((visibility("hidden"))) int nwv_bls_device_counters(nwv_ctx* ctx, 
                            (uint64_t)c->devs[device_index]->ordinal, c->devs.size()};
     for (int k = 0; k < cap && k < 6; k++) out[k] = v[k];
     return 6;
+}
+
+// the BLS12-381 engine's side of nwv_set_latency_max, nwv_latency_max, nwv_diag_qos and
+// nwv_diag_qos_priority (include/nwv.h)
+__attribute__((visibility("hidden"))) int nwv_bls_set_latency_max(nwv_ctx* ctx, size_t n) {
+    BlsCtx* c;
+    int rc = ctx_of(ctx, &c);
+    if (rc) return rc;
+    // below the shard minimum: a latency-class call is always one range
+    const size_t v = nwv::latency_clamp(n, bls_shard_min());
+    for (BlsDev* d : c->devs) d->latency_max.store(v);
+    return NWV_OK;
+}
+__attribute__((visibility("hidden"))) size_t nwv_bls_latency_max(const nwv_ctx* ctx) {
+    BlsCtx* c;
+    if (ctx_of(const_cast<nwv_ctx*>(ctx), &c)) return 0;
+    return c->devs[0]->latency_max.load();
+}
+__attribute__((visibility("hidden"))) int nwv_bls_diag_qos(nwv_ctx* ctx, int device_index, uint64_t out[8]) {
+    BlsCtx* c;
+    int rc = ctx_of(ctx, &c);
+    if (rc) return rc;
+    if (device_index < 0 || device_index >= (int)c->devs.size())
+        return nwv_internal_set_err(NWV_ERR_ARG, "bad device index");
+    c->devs[device_index]->pool.counters(out);
+    return NWV_OK;
+}
+__attribute__((visibility("hidden"))) int nwv_bls_diag_qos_priority(nwv_ctx* ctx, int device_index, int out[3]) {
+    BlsCtx* c;
+    int rc = ctx_of(ctx, &c);
+    if (rc) return rc;
+    if (device_index < 0 || device_index >= (int)c->devs.size())
+        return nwv_internal_set_err(NWV_ERR_ARG, "bad device index");
+    BlsDev* d = c->devs[device_index];
+    BLS_HIP(hipSetDevice(d->ordinal));
+    (void)nwv::stream_priority_range(out + 1);
+    if (const BlsLane* l = d->pool.first_reserved()) BLS_HIP(hipStreamGetPriority(l->stream, &out[0]));
+    return NWV_OK;
 }
 
 // the message-ring counters of the calling thread's last verify call on a context
@@ -2593,16 +2644,15 @@ static int verify_many_impl(nwv_ctx* ctx, size_t n_keys, const uint8_t* keys, si
     if (rc) return rc;
     // items split by index over the context's devices (bls_shard.h); a small call is one range on
     // the least-loaded device, the ranges of a larger one rotate (place.h)
-    static const size_t shard_min = [] {
-        const char* e = std::getenv("NWV_BLS_SHARD_MIN");
-        return e ? (size_t)std::strtoull(e, nullptr, 10) : (size_t)256;
-    }();
-    const auto ranges = bls_shard_ranges(n, c->devs.size(), shard_min);
+    const auto ranges = bls_shard_ranges(n, c->devs.size(), bls_shard_min());
     const auto tickets = nwv::place_ranges(*c->place, ranges, NWV_ENGINE_BLS);
     t_last_dev[ctx] = tickets[0].dev();
-    if (ranges.size() == 1)
-        return verify_on(*c->devs[tickets[0].dev()], n_keys, keys, n, sigs, pk_off, pk_cnt, pk_idx, n_idx, msg_base,
-                         msg_off, msg_len, msg_bytes, dst, dst_len, status, ah.n ? &ah : nullptr, mstat.v, mstat.a);
+    if (ranges.size() == 1) {
+        BlsDev& d = *c->devs[tickets[0].dev()];
+        // (a single range of at most nwv_latency_max items is latency class: lane_pool.h)
+        return verify_on(d, n_keys, keys, n, sigs, pk_off, pk_cnt, pk_idx, n_idx, msg_base, msg_off, msg_len, msg_bytes,
+                         dst, dst_len, status, ah.n ? &ah : nullptr, mstat.v, mstat.a, n <= d.latency_max.load());
+    }
     std::vector<std::string> err(ranges.size());
     std::vector<MsgStat> rstat(ranges.size());  // (the ranges run on threads of their own)
     rc = bls_for_ranges(ranges, [&](size_t k, size_t lo, size_t hi) -> int {
@@ -2942,7 +2992,7 @@ int nwv_bls_aggregate(nwv_ctx* ctx, size_t n, const uint8_t* sigs48, uint8_t out
     const nwv::Ticket ticket = holder < c->devs.size() ? nwv::Ticket(*c->place, holder, (uint64_t)n, NWV_ENGINE_BLS)
                                                        : nwv::Ticket(*c->place, (uint64_t)n, NWV_ENGINE_BLS);
     BlsDev* d = c->devs[ticket.dev()];
-    LaneLease lane(*d);
+    LaneLease lane(*d, n <= d->latency_max.load());
     if ((rc = lane.rc())) return rc;
     BlsLane& L = *lane;
     // scratch: records, statuses, the sum tree's two partial-sum levels, the output, decode statuses

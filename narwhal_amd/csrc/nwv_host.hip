@@ -29,6 +29,8 @@
 #include "each_kernels.hip"
 #include "group_keys.h"
 #include "keycache_alloc.h"
+#include "lane_pool.h"
+#include "lane_stream.h"
 #include "place.h"
 #include "shard.h"
 #include "stage_args.h"
@@ -56,6 +58,11 @@ void htrace(const char* what) {
 __attribute__((visibility("hidden"))) void nwv_bls_ctx_release(nwv_ctx* ctx);
 __attribute__((visibility("hidden"))) int nwv_bls_device_counters(nwv_ctx* ctx, int device_index, uint64_t* out,
                                                                   int cap);
+// the BLS12-381 engine's side of nwv_set_latency_max / nwv_latency_max / nwv_diag_qos[_priority]
+__attribute__((visibility("hidden"))) int nwv_bls_set_latency_max(nwv_ctx* ctx, size_t n);
+__attribute__((visibility("hidden"))) size_t nwv_bls_latency_max(const nwv_ctx* ctx);
+__attribute__((visibility("hidden"))) int nwv_bls_diag_qos(nwv_ctx* ctx, int device_index, uint64_t out[8]);
+__attribute__((visibility("hidden"))) int nwv_bls_diag_qos_priority(nwv_ctx* ctx, int device_index, int out[3]);
 __attribute__((visibility("hidden"))) int nwv_internal_set_err(int code, const char* msg) {
     g_last_error = msg;
     return code;
@@ -245,7 +252,8 @@ struct KeyCache {
 };
 
 // One device of a context: the basepoint table, the key cache and the pool of lanes (created on
-// demand, up to max_lanes; env NWV_LANES, default 4).
+// demand, up to max_lanes ordinary ones; env NWV_LANES, default 4; and up to NWV_LATENCY_LANES
+// reserved ones for latency-class calls, lane_pool.h).
 struct Gpu {
     int ordinal = -1;
     uint32_t flags = 0;
@@ -254,10 +262,11 @@ struct Gpu {
     // (shared: a staged batch unpins its slots when it is freed, which may be after the context)
     std::shared_ptr<KeyCache> kcp = std::make_shared<KeyCache>();
     KeyCache& kc = *kcp;
-    std::mutex mu;  // guards the pool
-    std::condition_variable cv;
-    std::vector<Lane*> lanes, idle;
+    nwv::LanePool<Lane> pool;
     size_t max_lanes = 4;
+    // reserved lanes' streams take the device's greatest priority (env NWV_LATENCY_PRIORITY=0:
+    // default priority, for A/B runs)
+    bool latency_priority = true;
     // staged-run prep chain (NWV_STAGE_CHAIN = k): a ring of k events; run r's prep waits for run
     // r - k's and records into slot r mod k
     std::mutex chain_mu;
@@ -341,8 +350,9 @@ void lane_close(Lane& d) {
     d.stream = nullptr;
 }
 
-// new lane of g (the calling thread has selected g's device)
-int lane_open(Gpu& g, Lane** out) {
+// new lane of g (the calling thread has selected g's device); a reserved lane's streams are created
+// at the device's greatest priority (lane_stream.h)
+int lane_open(Gpu& g, Lane** out, bool reserved = false) {
     *out = nullptr;
     auto* d = new (std::nothrow) Lane;
     if (!d) return set_err(NWV_ERR_OOM, "lane allocation");
@@ -350,10 +360,11 @@ int lane_open(Gpu& g, Lane** out) {
     d->ordinal = g.ordinal;
     d->flags = g.flags;
     d->btabp = &g.btab;
-    hipError_t e = hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking);
+    const bool high = reserved && g.latency_priority;
+    hipError_t e = nwv::lane_stream_create(&d->stream, high);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&d->hstage_ev, hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&d->b2stage_ev, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&d->aux, hipStreamNonBlocking);
+    if (e == hipSuccess) e = nwv::lane_stream_create(&d->aux, high);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&d->pksig_ev, hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&d->aux_ev, hipEventDisableTiming);
     if (e == hipSuccess &&
@@ -371,42 +382,27 @@ int lane_open(Gpu& g, Lane** out) {
     return NWV_OK;
 }
 
-// Exclusive use of one lane of g for the scope of a call: an idle lane, a new one while the pool
-// is below max_lanes, else wait for a lane to be returned.
+// Exclusive use of one lane of g for the scope of a call, by the rule of lane_pool.h: an idle lane,
+// a new one while the pool is below max_lanes, else wait for a lane to be returned; a latency-class
+// call tries the device's reserved lanes first.
 class LaneRef {
   public:
-    explicit LaneRef(Gpu& g) : g_(g) {
-        std::unique_lock<std::mutex> lk(g.mu);
-        for (;;) {
-            if (!g.idle.empty()) {
-                lane_ = g.idle.back();
-                g.idle.pop_back();
-                break;
+    explicit LaneRef(Gpu& g, bool latency = false) : g_(g) {
+        lane_ = g.pool.lease(latency, [&](bool reserved) -> Lane* {
+            Lane* l = nullptr;
+            if (hipSetDevice(g.ordinal) != hipSuccess) {
+                rc_ = set_err(NWV_ERR_HIP, "hipSetDevice");
+                return nullptr;
             }
-            if (g.lanes.size() < g.max_lanes) {
-                Lane* l = nullptr;
-                if (hipSetDevice(g.ordinal) != hipSuccess) {
-                    rc_ = set_err(NWV_ERR_HIP, "hipSetDevice");
-                    return;
-                }
-                if ((rc_ = lane_open(g, &l))) return;
-                g.lanes.push_back(l);
-                lane_ = l;
-                break;
-            }
-            g.cv.wait(lk);
-        }
-        lk.unlock();
-        rc_ = with_device(*lane_);
+            rc_ = lane_open(g, &l, reserved);
+            return l;
+        });
+        if (lane_) rc_ = with_device(*lane_);
     }
     ~LaneRef() {
         if (!lane_) return;
         kc_hold_release(*lane_);
-        {
-            std::lock_guard<std::mutex> lk(g_.mu);
-            g_.idle.push_back(lane_);
-        }
-        g_.cv.notify_one();
+        g_.pool.give_back(lane_);
     }
     LaneRef(const LaneRef&) = delete;
     LaneRef& operator=(const LaneRef&) = delete;
@@ -423,6 +419,8 @@ int gpu_open(Gpu& g, int ordinal, uint32_t flags) {
     g.ordinal = ordinal;
     g.flags = flags;
     if (const char* e = std::getenv("NWV_LANES")) g.max_lanes = (size_t)std::max(1L, std::strtol(e, nullptr, 10));
+    g.latency_priority = nwv::latency_priority_from_env();
+    g.pool.set_caps(g.max_lanes, nwv::latency_lanes_from_env());
     hipDeviceProp_t prop;
     NWV_HIP(hipGetDeviceProperties(&prop, ordinal));
     if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
@@ -432,8 +430,7 @@ int gpu_open(Gpu& g, int ordinal, uint32_t flags) {
     if (rc) return rc;
     Lane* l = nullptr;
     if ((rc = lane_open(g, &l))) return rc;
-    g.lanes.push_back(l);
-    g.idle.push_back(l);
+    g.pool.adopt(l);
     hipLaunchKernelGGL(k_base_table, dim3((BASE_TABLE_ENTRIES + 63) / 64), dim3(64), 0, l->stream,
                        g.btab.as<uint32_t>());
     if ((rc = g.comb.ensure((size_t)4 * MSM_PT_WORDS * COMB_TABLES * COMB_ENTRIES))) return rc;
@@ -447,12 +444,11 @@ int gpu_open(Gpu& g, int ordinal, uint32_t flags) {
 void gpu_close(Gpu& g) {
     if (g.ordinal < 0) return;
     (void)hipSetDevice(g.ordinal);
-    for (Lane* l : g.lanes) {
+    for (Lane* l : g.pool.all()) {
         lane_close(*l);
         delete l;
     }
-    g.lanes.clear();
-    g.idle.clear();
+    g.pool.clear();
     g.btab.release();
     g.comb.release();
     g.kc.recs.release();
@@ -1481,6 +1477,11 @@ struct nwv_ctx {
     // rejected registered-key batches of at most comb_pass_max signatures name their bad set with
     // k_ed_comb_pass (nwv_set_comb_pass_max, same clamp; every device object holds a copy)
     std::atomic<size_t> comb_pass_max{NWV_COMB_PASS_MAX_DEFAULT};
+    // calls of at most latency_max signatures (digest calls: messages, and at most
+    // latency_digest_bytes input bytes) lease from their device's reserved lanes
+    // (nwv_set_latency_max, same clamp; 0: off, the default)
+    std::atomic<size_t> latency_max{0};
+    size_t latency_digest_bytes = nwv::LATENCY_DIGEST_BYTES_DEFAULT;
     // the load of every device object, by which calls are placed (place.h; env NWV_PLACE, read at
     // nwv_init); the BLS12-381 engine shares it when it has as many device objects
     std::shared_ptr<nwv::PlaceTable> place;
@@ -1545,13 +1546,15 @@ struct nwv_staged {
 // context's devices (shard.h) and run fn(lane, lo, hi) for each: range 0 on the calling thread, the
 // others on one host thread each.  A call below 2 shard_min is one range, on the least-loaded
 // device; the ranges of a larger call rotate over the devices (place.h).  Every range holds its
-// ticket, taken before its lane is leased, until the call returns.
+// ticket, taken before its lane is leased, until the call returns.  A single-range call of at most
+// nwv_latency_max signatures is latency class (lane_pool.h).
 template <class Fn>
 static int for_shards(nwv_ctx* ctx, size_t n, Fn fn) {
     const auto ranges = nwv::ed_shard_ranges(n, ctx->devs.size(), ctx->shard_min);
     const auto tickets = nwv::place_ranges(*ctx->place, ranges);
+    const bool latency = ranges.size() == 1 && n <= ctx->latency_max.load();
     return nwv::for_ranges(ranges, [&](size_t k, size_t lo, size_t hi) -> int {
-        LaneRef lane(*ctx->devs[tickets[k].dev()]);
+        LaneRef lane(*ctx->devs[tickets[k].dev()], latency);
         const int rc = lane.rc();
         return rc ? rc : fn(*lane, lo, hi);
     });
@@ -1592,6 +1595,7 @@ static int init_devices(nwv_ctx** out, std::vector<int> ordinals, uint32_t flags
     ctx->shard_min = env_size("NWV_SHARD_MIN", ctx->shard_min, 1, SIZE_MAX);
     ctx->b2_shard_min = env_size("NWV_B2_SHARD_MIN", ctx->b2_shard_min, 1, SIZE_MAX);
     ctx->comb_batch_max = std::min<size_t>(NWV_COMB_BATCH_MAX_DEFAULT, ctx->shard_min - 1);
+    ctx->latency_digest_bytes = nwv::latency_digest_bytes_from_env();
     const size_t replicas = env_size("NWV_DEVICE_REPLICAS", 1, 1, 8);
     ctx->ordinals = ordinals;
     for (int o : ordinals)
@@ -1714,6 +1718,48 @@ int nwv_set_comb_pass_max(nwv_ctx* ctx, size_t n) {
     return NWV_OK;
 }
 size_t nwv_comb_pass_max(const nwv_ctx* ctx) { return ctx ? ctx->comb_pass_max.load() : 0; }
+int nwv_set_latency_max(nwv_ctx* ctx, int engine, size_t n) {
+    if (!ctx) return set_err(NWV_ERR_ARG, "null context");
+    if (engine == NWV_ENGINE_BLS) return nwv_bls_set_latency_max(ctx, n);
+    if (engine != NWV_ENGINE_ED25519) return set_err(NWV_ERR_ARG, "bad engine");
+    // below the shard minimum, as nwv_set_each_row_max: a latency-class signature call is always
+    // one range (a digest call is asked whether it is one where it is classed)
+    ctx->latency_max = nwv::latency_clamp(n, ctx->shard_min);
+    return NWV_OK;
+}
+size_t nwv_latency_max(const nwv_ctx* ctx, int engine) {
+    if (!ctx) return 0;
+    if (engine == NWV_ENGINE_BLS) return nwv_bls_latency_max(ctx);
+    return engine == NWV_ENGINE_ED25519 ? ctx->latency_max.load() : 0;
+}
+int nwv_diag_qos(nwv_ctx* ctx, int engine, int device_index, uint64_t* out, int cap) {
+    if (!ctx || (cap > 0 && !out) || cap < 0) return set_err(NWV_ERR_ARG, "bad argument");
+    uint64_t v[nwv::QOS_COUNTERS];
+    if (engine == NWV_ENGINE_BLS) {
+        const int rc = nwv_bls_diag_qos(ctx, device_index, v);
+        if (rc) return rc;
+    } else if (engine == NWV_ENGINE_ED25519) {
+        if (device_index < 0 || device_index >= (int)ctx->devs.size()) return set_err(NWV_ERR_ARG, "bad device index");
+        ctx->devs[device_index]->pool.counters(v);
+    } else {
+        return set_err(NWV_ERR_ARG, "bad engine");
+    }
+    for (int k = 0; k < cap && k < nwv::QOS_COUNTERS; k++) out[k] = v[k];
+    return nwv::QOS_COUNTERS;
+}
+int nwv_diag_qos_priority(nwv_ctx* ctx, int engine, int device_index, int out[3]) {
+    if (!ctx || !out) return set_err(NWV_ERR_ARG, "null argument");
+    out[0] = out[1] = out[2] = 0;
+    if (engine == NWV_ENGINE_BLS) return nwv_bls_diag_qos_priority(ctx, device_index, out);
+    if (engine != NWV_ENGINE_ED25519) return set_err(NWV_ERR_ARG, "bad engine");
+    if (device_index < 0 || device_index >= (int)ctx->devs.size()) return set_err(NWV_ERR_ARG, "bad device index");
+    Gpu* g = ctx->devs[device_index];
+    NWV_HIP(hipSetDevice(g->ordinal));
+    (void)nwv::stream_priority_range(out + 1);
+    // (a lane's streams live until nwv_free, and the runtime's query takes no part in their order)
+    if (const Lane* l = g->pool.first_reserved()) NWV_HIP(hipStreamGetPriority(l->stream, &out[0]));
+    return NWV_OK;
+}
 int nwv_diag_comb_pass(const nwv_ctx* ctx, uint64_t out[2]) {
     if (!ctx || !out) return set_err(NWV_ERR_ARG, "null argument");
     out[0] = out[1] = 0;
@@ -2993,6 +3039,18 @@ static int b2_stage(Lane& d, size_t n, const uint8_t* base, const uint64_t* off,
     return NWV_OK;
 }
 
+// a digest call of n messages is latency class: at most nwv_latency_max messages and at most
+// NWV_LATENCY_DIGEST_BYTES input bytes in total (worker-batch digests are bulk)
+static bool digest_latency(const nwv_ctx* ctx, size_t n, const uint64_t* len) {
+    if (n > ctx->latency_max.load()) return false;
+    uint64_t bytes = 0;
+    for (size_t i = 0; i < n; i++) {
+        bytes += len[i];
+        if (bytes > ctx->latency_digest_bytes) return false;
+    }
+    return true;
+}
+
 int nwv_blake2b256_many(nwv_ctx* ctx, size_t n, const uint8_t* base, const uint64_t* off,
                         const uint64_t* len, uint8_t* out) {
     if (!ctx || (n && (!off || !len || !out))) return set_err(NWV_ERR_ARG, "null argument");
@@ -3001,8 +3059,9 @@ int nwv_blake2b256_many(nwv_ctx* ctx, size_t n, const uint8_t* base, const uint6
     if (!base) base = empty;
     const auto ranges = nwv::shard_ranges(n, ctx->devs.size(), ctx->b2_shard_min, 1);
     const auto tickets = nwv::place_ranges(*ctx->place, ranges);
+    const bool latency = ranges.size() == 1 && digest_latency(ctx, n, len);
     return nwv::for_ranges(ranges, [&](size_t k, size_t lo, size_t hi) -> int {
-        LaneRef lane(*ctx->devs[tickets[k].dev()]);
+        LaneRef lane(*ctx->devs[tickets[k].dev()], latency);
         Lane& d = *lane;
         std::vector<uint64_t> roff;
         int rc = lane.rc();
@@ -3053,7 +3112,7 @@ int nwv_ed25519_verify_batch_keyed_digests(nwv_ctx* ctx, size_t n_pre, const uin
     uint8_t seed[32];
     fill_seed(seed32, seed);
     const nwv::Ticket ticket(*ctx->place, (uint64_t)n);
-    LaneRef lane(*ctx->devs[ticket.dev()]);
+    LaneRef lane(*ctx->devs[ticket.dev()], n <= ctx->latency_max.load());  // (a signature call)
     Lane& d = *lane;
     int rc = lane.rc();
     std::vector<uint64_t> roff;
@@ -3090,7 +3149,7 @@ int nwv_batch_digest_serialized(nwv_ctx* ctx, size_t n, const uint8_t* base, con
         return set_err(NWV_ERR_ARG, "null argument");
     if (n == 0) return NWV_OK;
     const nwv::Ticket ticket(*ctx->place, (uint64_t)n);
-    LaneRef lane(*ctx->devs[ticket.dev()]);
+    LaneRef lane(*ctx->devs[ticket.dev()], digest_latency(ctx, n, len));
     Lane& d = *lane;
     int rc = lane.rc();
     std::vector<uint64_t> roff;

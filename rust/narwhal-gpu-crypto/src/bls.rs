@@ -417,6 +417,23 @@ pub fn key_batch_min() -> usize {
     unsafe { ffi::nwv_bls_key_batch_min(ctx()) }
 }
 
+/// Let verification calls and aggregations of at most `n` items lease from each device's reserved
+/// lanes, whose streams run at the device's highest priority, so the Core's single verifies do not
+/// queue behind a synchronizer's large calls (0, the default, switches it off).
+pub fn latency_max_set(n: usize) -> Result<(), String> {
+    let rc = unsafe { ffi::nwv_set_latency_max(ctx(), ffi::NWV_ENGINE_BLS, n) };
+    if rc == ffi::NWV_OK {
+        Ok(())
+    } else {
+        Err(last_error())
+    }
+}
+
+/// The bound `latency_max_set` made, as in force (0: off).
+pub fn latency_max() -> usize {
+    unsafe { ffi::nwv_latency_max(ctx(), ffi::NWV_ENGINE_BLS) }
+}
+
 /// Of the calling thread's last verification call: groups formed, groups rejected, group items
 /// checked again per item, Miller loops the check ran, items in the groups (zeros when the
 /// key-transposed batch check did not run).

@@ -32,7 +32,7 @@ pub const NWV_ERR_EMPTY: c_int = -5;
 pub const NWV_ERR_LENGTH: c_int = -6;
 pub const NWV_ERR_REENTRANT: c_int = -7;
 pub const NWV_ABI_VERSION: c_int = 1;
-// nwv_diag_device_counters: the engine whose device objects are meant
+// nwv_diag_device_counters, nwv_set_latency_max, nwv_diag_qos: the engine that is meant
 pub const NWV_ENGINE_ED25519: c_int = 0;
 pub const NWV_ENGINE_BLS: c_int = 1;
 // nwv_init flags
@@ -200,6 +200,10 @@ extern "C" {
         out: *mut u64,
         cap: c_int,
     ) -> c_int;
+    pub fn nwv_set_latency_max(ctx: *mut NwvCtx, engine: c_int, n: usize) -> c_int;
+    pub fn nwv_latency_max(ctx: *const NwvCtx, engine: c_int) -> usize;
+    pub fn nwv_diag_qos(ctx: *mut NwvCtx, engine: c_int, device_index: c_int, out: *mut u64, cap: c_int) -> c_int;
+    pub fn nwv_diag_qos_priority(ctx: *mut NwvCtx, engine: c_int, device_index: c_int, out: *mut c_int) -> c_int;
     pub fn nwv_abi_version() -> c_int;
     pub fn nwv_last_error() -> *const c_char;
     // ---- Ed25519 verification (include/nwv.h)

@@ -437,6 +437,49 @@ pub fn keycache_register<K: AsRef<[u8]>>(committee: &[K]) -> Result<(), String> 
     }
 }
 
+/// Let Ed25519 signature calls of at most `n` signatures, and digest calls of at most `n` messages,
+/// lease from each device's reserved lanes, whose streams run at the device's highest priority: a
+/// primary's Core (one certificate, a header, a vote) then does not queue behind a block
+/// synchronizer's batches or a round's worker-batch digests.  0, the default, switches it off.
+pub fn latency_max_set(n: usize) -> Result<(), String> {
+    let rc = unsafe { ffi::nwv_set_latency_max(ctx(), ffi::NWV_ENGINE_ED25519, n) };
+    if rc == ffi::NWV_OK {
+        Ok(())
+    } else {
+        Err(last_error())
+    }
+}
+
+/// The bound `latency_max_set` made, as in force (0: off).
+pub fn latency_max() -> usize {
+    unsafe { ffi::nwv_latency_max(ctx(), ffi::NWV_ENGINE_ED25519) }
+}
+
+/// Lane counters of one device object of an engine (`ffi::NWV_ENGINE_*`): latency-class calls, those
+/// on a reserved lane, those that waited; other calls, those that waited; reserved lanes open, the
+/// reserved-lane cap, ordinary lanes open.
+pub fn qos_counters(engine: i32, device_index: i32) -> Result<[u64; 8], String> {
+    let mut out = [0u64; 8];
+    let rc = unsafe { ffi::nwv_diag_qos(ctx(), engine, device_index, out.as_mut_ptr(), 8) };
+    if rc == 8 {
+        Ok(out)
+    } else {
+        Err(last_error())
+    }
+}
+
+/// The priority of an engine's reserved lanes' streams on one device object (0 while none is open),
+/// then the device's greatest and least stream priority.
+pub fn qos_priority(engine: i32, device_index: i32) -> Result<[i32; 3], String> {
+    let mut out = [0i32; 3];
+    let rc = unsafe { ffi::nwv_diag_qos_priority(ctx(), engine, device_index, out.as_mut_ptr()) };
+    if rc == ffi::NWV_OK {
+        Ok(out)
+    } else {
+        Err(last_error())
+    }
+}
+
 // ------------------------------------------------------------------- worker digests --
 /// `Batch::digest` (types/src/primary.rs:65-73) of many batches in one GPU call: `batches[i]` is
 /// the concatenation of batch i's transactions.
