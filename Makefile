@@ -7,7 +7,8 @@ ARCH ?= gfx950
 BLS_SRC := narwhal_amd/csrc/nwv_bls.hip narwhal_amd/csrc/bls381.h narwhal_amd/csrc/bls_verify.h narwhal_amd/csrc/bls_group.h \
 	narwhal_amd/csrc/bls381_consts.h narwhal_amd/csrc/bls381_iso.h narwhal_amd/csrc/bls_wave.h \
 	narwhal_amd/csrc/bls_wave_prog.h narwhal_amd/csrc/bls_shard.h narwhal_amd/csrc/bls_msg_ring.h \
-	narwhal_amd/csrc/bls_apk_ring.h narwhal_amd/csrc/bls_key_batch.h include/nwv_bls.h
+	narwhal_amd/csrc/bls_apk_ring.h narwhal_amd/csrc/bls_key_batch.h narwhal_amd/csrc/bls_apk_dense.h \
+	include/nwv_bls.h
 # headers that both engines' translation units include (they stay in CSRC)
 BLS_SHARED := narwhal_amd/csrc/shard.h narwhal_amd/csrc/place.h narwhal_amd/csrc/lane_pool.h narwhal_amd/csrc/lane_stream.h
 CSRC := $(filter-out $(BLS_SRC),$(wildcard narwhal_amd/csrc/*.h narwhal_amd/csrc/*.hip narwhal_amd/csrc/*.cpp)) \
@@ -45,7 +46,8 @@ hostemu: tests/_build/libhostemu.so tests/_build/libsvcstub.so tests/_build/libb
 	tests/_build/libplace.so tests/_build/libkcalloc.so tests/_build/libgroupkeys.so tests/_build/libeachemu.so \
 	tests/_build/libblswbemu.so tests/_build/libblsmsgring.so tests/_build/libblsmremu.so \
 	tests/_build/libblsapkring.so tests/_build/libblsaremu.so tests/_build/libblskeybatch.so \
-	tests/_build/libblskbemu.so tests/_build/libblswvemu.so tests/_build/libcombpassemu.so \
+	tests/_build/libblskbemu.so tests/_build/libblsademu.so tests/_build/libblswvemu.so \
+	tests/_build/libcombpassemu.so \
 	tests/_build/libtailrcemu.so tests/_build/liblanepool.so
 # the wave interpreter one program at a time with its limb bounds evaluated (BLS_BOUNDS_CHECK;
 # tests/test_bls_wave_vectors_hostemu.py)
@@ -61,6 +63,10 @@ tests/_build/libblskbemu.so: tests/hostemu/bls_key_batch_hostemu.cpp tests/hoste
 		$(BLS_SRC) $(BLS_SHARED)
 	@mkdir -p tests/_build
 	$(HIPCC) -std=c++17 -O2 --offload-host-only -x hip -fPIC -shared -o $@ tests/hostemu/bls_key_batch_hostemu.cpp
+# the dense key-sum stage's per-group arithmetic and routing on the host (tests/test_bls_apk_dense_hostemu.py)
+tests/_build/libblsademu.so: tests/hostemu/bls_apk_dense_hostemu.cpp $(BLS_SRC) $(BLS_SHARED)
+	@mkdir -p tests/_build
+	$(HIPCC) -std=c++17 -O2 --offload-host-only -x hip -fPIC -shared -o $@ tests/hostemu/bls_apk_dense_hostemu.cpp
 # the message ring's bookkeeping (bls_msg_ring.h) with no HIP (tests/test_bls_msg_ring_host.py)
 tests/_build/libblsmsgring.so: tests/hostemu/bls_msg_ring_stub.cpp narwhal_amd/csrc/bls_msg_ring.h
 	@mkdir -p tests/_build

@@ -113,6 +113,25 @@ size_t nwv_bls_key_batch_min(const nwv_ctx* ctx);
  * key entries plus one signature entry a group), out[4] items in the groups (zeros when the check
  * did not run) */
 int nwv_bls_last_key_batch(nwv_ctx* ctx, uint64_t out[5]);
+/* The dense key-sum stage.  A large wave call (as above) of at least n items -- or a device's
+ * share of one -- sums its items' keys with several items to a wave instead of one wave an item:
+ * the items whose keys all sit in the serving device's key cache and whose list names at least two
+ * keys get L lanes each (L = 4, 8 or 16: the largest that still fills 65,536 lanes, else 4; env
+ * NWV_BLS_APK_LANES, read once, forces one), every other item keeps the per-item kernel.  When
+ * every key of the call's key table is registered, an item whose list is strictly ascending and
+ * names more than half of the table takes its sum as the table's total minus the keys it leaves
+ * out; every other item is summed directly, so repeated and unsorted lists keep their
+ * multiplicity.  The sums, and every status, are those of the per-item kernel; the pairing paths
+ * (per item, nwv_bls_set_wave_batch_min, nwv_bls_set_key_batch_min) read them unchanged.  n = 0
+ * (the default) turns it off: every call then takes exactly the launches it takes without this
+ * setting.  Calls of at most NWV_BLS_WAVE_MAX items never take it. */
+int nwv_bls_set_apk_dense_min(nwv_ctx* ctx, size_t n);
+size_t nwv_bls_apk_dense_min(const nwv_ctx* ctx);
+/* the dense key-sum stage of the calling thread's last nwv_bls_verify_many call (range 0's device
+ * when the call split): out[0] items summed directly by the dense kernel, out[1] items summed by
+ * complement, out[2] items left to the per-item kernel, out[3] lanes an item (zeros when the stage
+ * did not run) */
+int nwv_bls_last_apk_dense(nwv_ctx* ctx, uint64_t out[4]);
 /* keys of the last nwv_bls_verify_many call: out[0] key-list entries found in the key cache,
  * out[1] distinct keys the call decoded itself */
 int nwv_bls_last_keys(nwv_ctx* ctx, uint64_t out[2]);

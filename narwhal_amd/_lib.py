@@ -133,6 +133,10 @@ def load():
         "nwv_latency_max": ([_vp, _i32], _sz),
         "nwv_diag_qos": ([_vp, _i32, _i32, _vp, _i32], _i32),
         "nwv_diag_qos_priority": ([_vp, _i32, _i32, _vp], _i32),
+        # the dense key-sum stage of large BLS calls (Bls.set_apk_dense_min, last_apk_dense)
+        "nwv_bls_set_apk_dense_min": ([_vp, _sz], _i32),
+        "nwv_bls_apk_dense_min": ([_vp], _sz),
+        "nwv_bls_last_apk_dense": ([_vp, _vp], _i32),
     }
     for name, (args, res) in newer.items():
         f = getattr(lib, name, None)

@@ -227,6 +227,21 @@ class Bls:
         _lib._check(self.lib.nwv_bls_last_key_batch(self._h, out.ctypes.data))
         return tuple(int(x) for x in out)
 
+    # the dense key-sum stage of large calls (several items a wave, a quorum's sum as the key
+    # table's total minus the absent keys): off at 0
+    def set_apk_dense_min(self, n):
+        _lib._check(self.lib.nwv_bls_set_apk_dense_min(self._h, n))
+
+    def apk_dense_min(self):
+        return int(self.lib.nwv_bls_apk_dense_min(self._h))
+
+    def last_apk_dense(self):
+        """(items summed directly by the dense kernel, items summed by complement, items left to the
+        per-item kernel, lanes an item) of the last verify_many; zeros when the stage did not run"""
+        out = np.zeros(4, dtype=np.uint64)
+        _lib._check(self.lib.nwv_bls_last_apk_dense(self._h, out.ctypes.data))
+        return tuple(int(x) for x in out)
+
     # the committee key cache: register at epoch start, reset at an epoch change
     def register_keys(self, keys):
         kb = _arr(b"".join(keys))

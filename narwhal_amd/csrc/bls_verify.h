@@ -620,6 +620,132 @@ NWV_HD uint32_t kb_key_q_word(const uint32_t* key_rec, int wd) {
     return wd < 4 * NL ? key_rec[wd] : wd < 5 * NL ? one.l[wd - 4 * NL] : 0u;
 }
 
+// ---- dense key sums of large calls (nwv_bls_set_apk_dense_min): `lanes` lanes per
+// item (4, 8 or 16), each adding its stride of the item's keys' affine [h_eff] pk records into a
+// Jacobian accumulator; the partial sums meet in a tree of log2 lanes levels (lane s < h takes lane
+// s + h's, h = lanes / 2 .. 1).  An item over more than half of a wholly registered key table whose
+// list is strictly ascending sums the ABSENT keys instead, found from the list's gaps, and takes
+// total - that sum.
+//
+// mixed addition (madd-2007-bl: the second point affine, Z2 = 1) with jac_add's exceptional cases:
+// exact for equal points (doubling) and opposite ones (the identity)
+template <class F> BLS_NOINLINE jac<F> jac_add_affine(const jac<F>& a, const F& x2, const F& y2) {
+    using O = ops<F>;
+    if (a.inf) return jac_from_affine(x2, y2);
+    const F z1z1 = O::sqr(a.z);
+    const F u2 = O::mul(x2, z1z1), s2 = O::mul(O::mul(y2, a.z), z1z1);
+    if (O::eq(a.x, u2)) {
+        if (O::eq(a.y, s2)) return jac_dbl(a);
+        jac<F> o = a;
+        o.inf = true;
+        return o;
+    }
+    const F h = O::sub(u2, a.x), hh = O::sqr(h);
+    F i = O::add(hh, hh);
+    i = O::add(i, i);
+    const F j = O::mul(h, i);
+    F rr = O::sub(s2, a.y);
+    rr = O::add(rr, rr);
+    const F v = O::mul(a.x, i);
+    jac<F> o;
+    o.inf = false;
+    o.x = O::sub(O::sub(O::sub(O::sqr(rr), j), v), v);
+    const F yj = O::mul(a.y, j);
+    o.y = O::sub(O::mul(rr, O::sub(v, o.x)), O::add(yj, yj));
+    o.z = O::sub(O::sub(O::sqr(O::add(a.z, h)), z1z1), hh);
+    return o;
+}
+// the records a dense item's key numbers name: key number k of the call's table sits in cache slot
+// ktab[k] (a slot below `cap`; anything else is a key the cache does not hold)
+struct DenseKeys {
+    const uint32_t* hrc;   // the cache's [h_eff] pk records (G2_REC_WORDS per slot)
+    const int32_t* sc;     // the slots' statuses
+    const uint32_t* ktab;  // the call's key table, n_keys entries
+    uint32_t n_keys, cap;
+};
+NWV_HD jac<fp2> blsd_identity() {
+    jac<fp2> a;
+    a.inf = true;
+    a.x = a.y = a.z = f2_zero();
+    return a;
+}
+NWV_HD jac<fp2> blsd_add_key(const DenseKeys& t, const jac<fp2>& acc, uint32_t k) {
+    fp2 x, y;
+    ld_g2(t.hrc + (size_t)G2_REC_WORDS * t.ktab[k], x, y);
+    return jac_add_affine(acc, x, y);
+}
+// the key table's total (k_blsd_total): lane `lane` of `lanes`' share, keys lane, lane + lanes, ...;
+// ok turns false at a key that is not cached with status OK (the total is then not used)
+NWV_HD jac<fp2> blsd_total_lane(const DenseKeys& t, uint32_t lane, uint32_t lanes, bool& ok) {
+    jac<fp2> acc = blsd_identity();
+    ok = true;
+    for (uint32_t k = lane; k < t.n_keys; k += lanes) {
+        const uint32_t s = t.ktab[k];
+        if (s >= t.cap || t.sc[s] != ST_OK) {
+            ok = false;
+            break;
+        }
+        acc = blsd_add_key(t, acc, k);
+    }
+    return acc;
+}
+// this lane's positions of the list (key numbers idx[0 .. cnt)) each follow a smaller number: true
+// in every lane of the item <=> the list is strictly ascending
+NWV_HD bool blsd_lane_ascending(const uint32_t* idx, uint32_t cnt, uint32_t lane, uint32_t lanes) {
+    for (uint32_t j = lane; j < cnt; j += lanes)
+        if (j && idx[j - 1] >= idx[j]) return false;
+    return true;
+}
+// the lane's share of the list summed directly, in list order (multiplicity kept); first_bad = the
+// first of its positions whose key's status is not OK (the lane stops there), else 0xffffffff
+NWV_HD jac<fp2> blsd_lane_direct(const DenseKeys& t, const uint32_t* idx, uint32_t cnt, uint32_t lane, uint32_t lanes,
+                                 uint32_t& first_bad) {
+    jac<fp2> acc = blsd_identity();
+    first_bad = 0xffffffffu;
+    for (uint32_t j = lane; j < cnt; j += lanes) {
+        if (t.sc[t.ktab[idx[j]]] != ST_OK) {
+            first_bad = j;
+            break;
+        }
+        acc = blsd_add_key(t, acc, idx[j]);
+    }
+    return acc;
+}
+// the lane's share of the keys a strictly ascending list leaves out: the absent keys in ascending
+// order, found from the list's gaps, are dealt to the lanes in turn (the r-th absent key to lane
+// r % lanes).  One addition per trip of the outer loop: the walk to the lane's next key is index
+// arithmetic only, so the lanes of a wave -- which hold different items -- run their additions
+// together however their gaps differ.
+NWV_HD jac<fp2> blsd_lane_absent(const DenseKeys& t, const uint32_t* idx, uint32_t cnt, uint32_t lane, uint32_t lanes) {
+    jac<fp2> acc = blsd_identity();
+    uint32_t k = 0, j = 0, rank = 0;  // the next key number, the next list position, absent keys passed
+    for (;;) {
+        uint32_t mine = 0xffffffffu;
+        while (k < t.n_keys && mine == 0xffffffffu) {
+            if (j < cnt && idx[j] == k) j++;
+            else if (rank++ % lanes == lane) mine = k;
+            k++;
+        }
+        if (mine == 0xffffffffu) break;
+        acc = blsd_add_key(t, acc, mine);
+    }
+    return acc;
+}
+// lane 0's end of an item: the tree's sum (of the absent keys when comp: the item's sum is then
+// total - it), the item's first bad position -> its status, with the record zeroed unless OK
+NWV_HD int32_t blsd_finish(const DenseKeys& t, const uint32_t* idx, jac<fp2>& acc, bool comp, const jac<fp2>& total,
+                           uint32_t first_bad) {
+    if (comp) {
+        acc.y = f2_neg(acc.y);
+        acc = jac_add(total, acc);
+    }
+    int32_t status = ST_OK;
+    if (first_bad != 0xffffffffu) status = t.sc[t.ktab[idx[first_bad]]];
+    else if (acc.inf) status = ST_PK_INFINITY;
+    if (status != ST_OK) acc = blsd_identity();
+    return status;
+}
+
 // ---- AggregateAuthenticator::aggregate (types/src/primary.rs:476-477) on a wave: g1_sum16 adds
 // G1SUM_N points with complete formulas (the identity and equal points need no branches); point k
 // sits in slots g1sum_slot(k) + 0..2 as (X : Y : Z) and the sum lands in U

@@ -39,6 +39,7 @@
 #include "bls_msg_ring.h"
 #include "bls_apk_ring.h"
 #include "bls_key_batch.h"
+#include "bls_apk_dense.h"
 #include "lane_pool.h"
 #include "lane_stream.h"
 #include "place.h"
@@ -1026,6 +1027,76 @@ __global__ __launch_bounds__(64) void k_blsw_apk(uint32_t n, KeyTab kt, const ui
     if (blockIdx.x >= n) return;
     blsw_apk_item(xa, blockIdx.x, kt, pk_off, pk_cnt, pk_idx, kmode, rec, st_apk);
 }
+// the same over an item list (the items the dense key-sum stage leaves to the per-item code)
+__global__ __launch_bounds__(64) void k_blsw_apk_list(uint32_t n, const uint32_t* item, KeyTab kt,
+                                                      const uint32_t* pk_off, const uint32_t* pk_cnt,
+                                                      const uint32_t* pk_idx, const uint32_t* kmode, uint32_t* rec,
+                                                      int32_t* st_apk) {
+    __shared__ uint32_t xa[32 * G2J_WORDS];
+    if (blockIdx.x >= n) return;
+    blsw_apk_item(xa, item[blockIdx.x], kt, pk_off, pk_cnt, pk_idx, kmode, rec, st_apk);
+}
+// ---- the dense key-sum stage of large wave calls (nwv_bls_set_apk_dense_min, DESIGN §3.6.5;
+// bls_verify.h's blsd_* steps, bls_apk_dense.h's routing)
+//
+// the key table's total, one workgroup: tot = the sum of every key's [h_eff] pk record as a
+// G2J_WORDS record, tot[G2J_WORDS] = 1 when every key of the table is cached with status OK (else
+// 0: no item then takes its sum from the total)
+constexpr int DT_WORDS = G2J_WORDS + 1;
+__global__ __launch_bounds__(64) void k_blsd_total(DenseKeys t, uint32_t* tot) {
+    __shared__ uint32_t xa[32 * G2J_WORDS];
+    const int lane = (int)threadIdx.x;
+    bool ok;
+    jac<fp2> acc = blsd_total_lane(t, (uint32_t)lane, 64u, ok);
+    const bool all_ok = __all(ok);
+#pragma unroll 1
+    for (int h = 32; h >= 1; h >>= 1) {
+        __syncthreads();
+        if (lane >= h && lane < 2 * h) st_g2j(xa + (lane - h) * G2J_WORDS, acc);
+        __syncthreads();
+        if (lane < h) acc = jac_add(acc, ld_g2j(xa + lane * G2J_WORDS));
+    }
+    if (lane != 0) return;
+    if (!all_ok) acc = blsd_identity();
+    st_g2j(tot, acc);
+    tot[G2J_WORDS] = all_ok ? 1u : 0u;
+}
+// L lanes an item, 64 / L items a wave: item item[q]'s key sum over its list of key NUMBERS
+// (idx0: the caller's indices into the call's key table, not cache slots), written where
+// blsw_apk_item writes it.  mode[q] = 1 when the sum came from the total (a strictly ascending
+// list over more than half of a wholly registered table), else 0 (summed directly).
+template <int L>
+__global__ __launch_bounds__(64) void k_blsd_apk(uint32_t n, const uint32_t* item, DenseKeys t, const uint32_t* pk_off,
+                                                 const uint32_t* pk_cnt, const uint32_t* idx0, const uint32_t* tot,
+                                                 uint32_t* rec, int32_t* st_apk, uint32_t* mode) {
+    static_assert(L == 4 || L == 8 || L == 16, "lanes per item");
+    constexpr int PER = 64 / L;
+    __shared__ uint32_t lds[32 * G2J_WORDS];
+    const uint32_t s = threadIdx.x % L, q = blockIdx.x * PER + threadIdx.x / L;
+    uint32_t* xa = lds + (threadIdx.x / L) * (L / 2) * G2J_WORDS;  // the group's L / 2 records
+    const bool live = q < n;  // (a lane past the list walks nothing: every lane reaches the barriers)
+    const uint32_t i = live ? item[q] : 0u;
+    const uint32_t cnt = live ? pk_cnt[i] : 0u;
+    const uint32_t* idx = idx0 + (live ? pk_off[i] : 0u);
+    bool asc = blsd_lane_ascending(idx, cnt, s, L);
+    for (int m = L / 2; m >= 1; m >>= 1) asc = __shfl_xor((int)asc, m) && asc;
+    const bool comp = asc && tot[G2J_WORDS] != 0 && cnt > t.n_keys / 2;
+    uint32_t first_bad = 0xffffffffu;
+    jac<fp2> acc = comp ? blsd_lane_absent(t, idx, cnt, s, L) : blsd_lane_direct(t, idx, cnt, s, L, first_bad);
+    for (int m = L / 2; m >= 1; m >>= 1) first_bad = min(first_bad, (uint32_t)__shfl_xor((int)first_bad, m));
+#pragma unroll 1
+    for (int h = L / 2; h >= 1; h >>= 1) {
+        __syncthreads();
+        if (s >= (uint32_t)h && s < 2u * h) st_g2j(xa + (s - h) * G2J_WORDS, acc);
+        __syncthreads();
+        if (s < (uint32_t)h) acc = jac_add(acc, ld_g2j(xa + s * G2J_WORDS));
+    }
+    if (s != 0 || !live) return;
+    const int32_t status = blsd_finish(t, idx, acc, comp, comp ? ld_g2j(tot) : acc, first_bad);
+    st_g2j(rec + (size_t)G2J_WORDS * i, acc);
+    st_apk[i] = status;
+    mode[q] = comp ? 1u : 0u;
+}
 // hash to G1 (blocks [0, n)) and the key sums (blocks [n, 2n)) as one launch (one stream per
 // call side): independent waves, the LDS of the larger of the two
 __global__ __launch_bounds__(64) void k_blsw_pre(uint32_t n, const uint8_t* msg, const uint64_t* off,
@@ -1499,6 +1570,11 @@ struct BlsDev {
     std::atomic<size_t> key_batch_min{0};
     // its last call: groups formed, rejected, items re-checked, Miller loops, items in the groups
     uint64_t last_kbatch[5] = {0, 0, 0, 0, 0};
+    // nwv_bls_set_apk_dense_min: large wave calls of at least this many items sum their keys in the
+    // dense stage (k_blsd_total, k_blsd_apk, k_blsw_apk_list) in place of k_blsw_apk (0: never)
+    std::atomic<size_t> apk_dense_min{0};
+    // its last call: items summed directly, by complement, left to the per-item kernel, lanes an item
+    uint64_t last_apkd[4] = {0, 0, 0, 0};
 };
 // the BLS engine's state of one context: one BlsDev per device of the context (nwv_init with
 // several devices shards nwv_bls_verify_many by item index, bls_shard.h).  Diagnostic / test hook:
@@ -1795,6 +1871,14 @@ int verify_on(BlsDev& d, size_t n_keys, const uint8_t* keys, size_t n, const uin
         return (uint32_t)(v > 1024 ? 1024 : v);
     }();
     const size_t kb_min = d.key_batch_min.load(std::memory_order_relaxed);
+    // the dense key-sum stage (bls_apk_dense.h): large wave calls of at least
+    // nwv_bls_set_apk_dense_min items; NWV_BLS_APK_LANES forces the lanes an item gets (4, 8, 16)
+    static const unsigned long ad_forced = [] {
+        const char* e = std::getenv("NWV_BLS_APK_LANES");
+        return e ? std::strtoul(e, nullptr, 10) : 0ul;
+    }();
+    const size_t ad_min = d.apk_dense_min.load(std::memory_order_relaxed);
+    const bool ad_run = wavem && !wave_small && ad_min > 0 && n >= ad_min;
     int rc;
     // the call's key table: cache slots (lookups only) or scratch entries KC_CAP + j
     std::shared_lock<std::shared_mutex> kc_hold(d.kc.mu);  // records stay put while our kernels read them
@@ -1837,6 +1921,12 @@ int verify_on(BlsDev& d, size_t n_keys, const uint8_t* keys, size_t n, const uin
         for (uint32_t j = 0; j < pk_cnt[i] && all; j++) all = remap[pk_off[i] + j] < KC_CAP;
         kmode[i] = all ? 1u : 0u;
     }
+    // the dense key-sum stage's item lists and lanes (the stage reads the caller's key numbers and
+    // the key table itself: an ascending list is ascending in those, not in cache slots)
+    nwv::ApkDenseSplit ads;
+    if (ad_run) nwv::apk_dense_split(n, kside ? kmode.data() : nullptr, pk_cnt, ads);
+    const size_t n_dn = ads.dense.size(), n_rest = ads.rest.size();
+    const uint32_t ad_lanes = ad_run ? nwv::apk_dense_lanes(n_dn, ad_forced) : 0;
     const size_t n_dec = fill_slot.size();  // keys decoded by this call
     // verified signatures stay decoded in the device's ring (BlsSigCache) for aggregates
     // (n <= 1,024 whatever NWV_BLS_WAVE_MAX says: the calls in flight on a device's lanes then hold
@@ -1989,7 +2079,13 @@ int verify_on(BlsDev& d, size_t n_keys, const uint8_t* keys, size_t n, const uin
     // (one section for everything the ring adds: a single verification still fits stage_h2d's arguments)
     const size_t o_ring = use_ring ? a.add(rsec.data(), rsec.size()) : 0;
     const size_t o_fill = n_fill ? a.add(a_fill.data(), 8 * n_fill) : 0;
-    if ((rc = L.stage.ensure(al256(a.total) + 64 + 4 * wb_ng)) || (rc = L.in.ensure(a.total))) return rc;
+    const size_t o_dlist = n_dn ? a.add(ads.dense.data(), 4 * n_dn) : 0,
+                 o_rlist = n_dn && n_rest ? a.add(ads.rest.data(), 4 * n_rest) : 0,
+                 o_idx0 = n_dn ? a.add(pk_idx, 4 * n_idx) : 0, o_ktab = n_dn ? a.add(ktab.data(), 4 * n_keys) : 0;
+    // (pinned, behind the arena: the batch verdict word, the wave batch check's group verdicts, the
+    // dense key sums' per-item modes)
+    const size_t h_dmode = al256(al256(a.total) + 64 + 4 * wb_ng);
+    if ((rc = L.stage.ensure(h_dmode + 4 * n_dn)) || (rc = L.in.ensure(a.total))) return rc;
     uint8_t* h = static_cast<uint8_t*>(L.stage.p);
     for (size_t k = 0; k < a.parts.size(); k++)
         if (a.parts[k].second) std::memcpy(h + a.offs[k], a.parts[k].first, a.parts[k].second);
@@ -2010,7 +2106,9 @@ int verify_on(BlsDev& d, size_t n_keys, const uint8_t* keys, size_t n, const uin
                  w_wf = w_wb, w_wp = al256(w_wf + 4 * FB_REC_WORDS * wb_m), w_wj = al256(w_wp + 4 * G1H_REC_WORDS * wb_m),
                  w_wsg = al256(w_wj + 4 * G1J_REC_WORDS * (wbatch ? n : 0)),
                  w_winb = al256(w_wsg + 4 * G1_REC_WORDS * wb_ng), w_wgok = al256(w_winb + 4 * (wbatch ? n : 0)),
-                 w_end = w_wgok + 4 * wb_ng + 4;
+                 // the dense key sums' scratch: the key table's total and flag, the items' modes
+                 w_dtot = al256(w_wgok + 4 * wb_ng + 4), w_dmode = al256(w_dtot + 4 * (n_dn ? DT_WORDS : 0)),
+                 w_end = w_dmode + 4 * n_dn + 4;
     if ((rc = L.work.ensure(w_end))) return rc;
     uint8_t* in = static_cast<uint8_t*>(L.in.p);
     uint8_t* w = static_cast<uint8_t*>(L.work.p);
@@ -2046,7 +2144,7 @@ int verify_on(BlsDev& d, size_t n_keys, const uint8_t* keys, size_t n, const uin
     bool untimed = false;  // a small call that recorded no stage events (set on that path only)
     auto trec = [&](int k, hipStream_t s) { return no_timing ? hipSuccess : hipEventRecord(L.ev[k], s); };
     // stage times of the completed call, its path and key counts -> the device's "last call"
-    uint64_t wb_stat[3] = {0, 0, 0}, kb_stat[5] = {0, 0, 0, 0, 0};
+    uint64_t wb_stat[3] = {0, 0, 0}, kb_stat[5] = {0, 0, 0, 0, 0}, ad_stat[4] = {0, 0, 0, 0};
     auto finish = [&](int path_done) -> int {
         const int pairs[5][2] = {{0, 1}, {3, 4}, {5, 6}, {1, 2}, {7, 8}};  // keys, sigs, h2c, apk, pairing
         double ms5[5] = {0, 0, 0, 0, 0};
@@ -2062,6 +2160,7 @@ int verify_on(BlsDev& d, size_t n_keys, const uint8_t* keys, size_t n, const uin
         d.last_keys[1] = n_dec;
         std::memcpy(d.last_batch, wb_stat, sizeof wb_stat);
         std::memcpy(d.last_kbatch, kb_stat, sizeof kb_stat);
+        std::memcpy(d.last_apkd, ad_stat, sizeof ad_stat);
         return NWV_OK;
     };
     BLS_HIP(nwv_stage::stage_h2d(in, h, a.total, s0));  // small calls: through kernel arguments
@@ -2177,7 +2276,26 @@ int verify_on(BlsDev& d, size_t n_keys, const uint8_t* keys, size_t n, const uin
                            reinterpret_cast<const uint32_t*>(in + o_kslot), const_cast<uint32_t*>(kt.rs),
                            const_cast<int32_t*>(kt.ss));
     BLS_HIP(hipEventRecord(L.ev[1], s1));
-    if (wavem)
+    auto* dtot = reinterpret_cast<uint32_t*>(w + w_dtot);
+    auto* dmode = reinterpret_cast<uint32_t*>(w + w_dmode);
+    if (wavem && n_dn) {
+        // the dense stage: the key table's total, the dense items L lanes each, then the items
+        // left to the per-item code through their list (all three write disjoint records)
+        const DenseKeys dk{kt.hrc, kt.sc, reinterpret_cast<const uint32_t*>(in + o_ktab), (uint32_t)n_keys, KC_CAP};
+        const auto* d_list = reinterpret_cast<const uint32_t*>(in + o_dlist);
+        const auto* p_off = reinterpret_cast<const uint32_t*>(in + o_off);
+        const auto* p_cnt = reinterpret_cast<const uint32_t*>(in + o_cnt);
+        const auto* p_idx0 = reinterpret_cast<const uint32_t*>(in + o_idx0);
+        hipLaunchKernelGGL(k_blsd_total, dim3(1), dim3(64), 0, s1, dk, dtot);
+        const unsigned per = 64 / ad_lanes, blocks = (unsigned)((n_dn + per - 1) / per);
+        auto* kern = ad_lanes == 16 ? k_blsd_apk<16> : ad_lanes == 8 ? k_blsd_apk<8> : k_blsd_apk<4>;
+        hipLaunchKernelGGL(kern, dim3(blocks), dim3(64), 0, s1, (uint32_t)n_dn, d_list, dk, p_off, p_cnt, p_idx0,
+                           (const uint32_t*)dtot, ajrec, sapk, dmode);
+        if (n_rest)
+            hipLaunchKernelGGL(k_blsw_apk_list, dim3((unsigned)n_rest), dim3(64), 0, s1, (uint32_t)n_rest,
+                               reinterpret_cast<const uint32_t*>(in + o_rlist), kt, p_off, p_cnt,
+                               reinterpret_cast<const uint32_t*>(in + o_idx), km, ajrec, sapk);
+    } else if (wavem)
         hipLaunchKernelGGL(k_blsw_apk, dim3((unsigned)n), dim3(64), 0, s1, (uint32_t)n, kt,
                            reinterpret_cast<const uint32_t*>(in + o_off), reinterpret_cast<const uint32_t*>(in + o_cnt),
                            reinterpret_cast<const uint32_t*>(in + o_idx), km, ajrec, sapk);
@@ -2418,7 +2536,14 @@ int verify_on(BlsDev& d, size_t n_keys, const uint8_t* keys, size_t n, const uin
                            (const uint32_t*)srec, nullptr, nullptr);
         BLS_HIP(hipGetLastError());
         BLS_HIP(hipMemcpyAsync(status, st, 4 * n, hipMemcpyDeviceToHost, s0));
+        const uint32_t* h_dm = reinterpret_cast<const uint32_t*>(h + h_dmode);
+        if (n_dn) BLS_HIP(hipMemcpyAsync(h + h_dmode, dmode, 4 * n_dn, hipMemcpyDeviceToHost, s0));
         BLS_HIP(hipStreamSynchronize(s0));
+        if (ad_run) {
+            for (size_t q = 0; q < n_dn; q++) ad_stat[h_dm[q] ? 1 : 0]++;
+            ad_stat[2] = n_rest;
+            ad_stat[3] = ad_lanes;
+        }
         return finish(path_done);
     }
     // main: signatures, then the join
@@ -2896,6 +3021,30 @@ int nwv_bls_last_key_batch(nwv_ctx* ctx, uint64_t out[5]) {
     if (rc) return rc;
     std::lock_guard<std::mutex> g(d->stat_mu);
     for (int k = 0; k < 5; k++) out[k] = d->last_kbatch[k];
+    return NWV_OK;
+}
+
+int nwv_bls_set_apk_dense_min(nwv_ctx* ctx, size_t n) {
+    BlsCtx* c;
+    int rc = ctx_of(ctx, &c);
+    if (rc) return rc;
+    for (BlsDev* d : c->devs) d->apk_dense_min.store(n, std::memory_order_relaxed);
+    return NWV_OK;
+}
+
+size_t nwv_bls_apk_dense_min(const nwv_ctx* ctx) {
+    BlsCtx* c;
+    if (ctx_of(const_cast<nwv_ctx*>(ctx), &c)) return 0;
+    return c->devs[0]->apk_dense_min.load(std::memory_order_relaxed);
+}
+
+int nwv_bls_last_apk_dense(nwv_ctx* ctx, uint64_t out[4]) {
+    if (!out) return nwv_internal_set_err(NWV_ERR_ARG, "null argument");
+    BlsDev* d;
+    int rc = last_dev_of(ctx, &d);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> g(d->stat_mu);
+    for (int k = 0; k < 4; k++) out[k] = d->last_apkd[k];
     return NWV_OK;
 }
 

@@ -447,6 +447,37 @@ pub fn last_key_batch() -> Result<[u64; 5], String> {
     }
 }
 
+/// Let large verification calls (more than 1,024 items) of at least `n` items sum their items'
+/// keys in the dense stage: several items to a wave, and a quorum over a wholly registered
+/// committee as the committee's total minus the absent keys (0, the default, switches it off).
+/// Sums and statuses are those of the per-item key-sum kernel.
+pub fn apk_dense_min_set(n: usize) -> Result<(), String> {
+    let rc = unsafe { ffi::nwv_bls_set_apk_dense_min(ctx(), n) };
+    if rc == ffi::NWV_OK {
+        Ok(())
+    } else {
+        Err(last_error())
+    }
+}
+
+/// The setting `apk_dense_min_set` made (0: off).
+pub fn apk_dense_min() -> usize {
+    unsafe { ffi::nwv_bls_apk_dense_min(ctx()) }
+}
+
+/// Of the calling thread's last verification call: items the dense kernel summed directly, items
+/// it summed by complement, items left to the per-item kernel, lanes an item (zeros when the dense
+/// key-sum stage did not run).
+pub fn last_apk_dense() -> Result<[u64; 4], String> {
+    let mut out = [0u64; 4];
+    let rc = unsafe { ffi::nwv_bls_last_apk_dense(ctx(), out.as_mut_ptr()) };
+    if rc == ffi::NWV_OK {
+        Ok(out)
+    } else {
+        Err(last_error())
+    }
+}
+
 /// Hash messages into the ring ahead of the calls that verify over them.  The Proposer calls this
 /// with the certificate digest of the header it has just made: that header never passes
 /// `sanitize_header`, and its votes and certificate are the hits.  A no-op with the ring off.

@@ -346,6 +346,9 @@ extern "C" {
     pub fn nwv_bls_set_key_batch_min(ctx: *mut NwvCtx, n: usize) -> c_int;
     pub fn nwv_bls_key_batch_min(ctx: *const NwvCtx) -> usize;
     pub fn nwv_bls_last_key_batch(ctx: *mut NwvCtx, out: *mut u64) -> c_int;
+    pub fn nwv_bls_set_apk_dense_min(ctx: *mut NwvCtx, n: usize) -> c_int;
+    pub fn nwv_bls_apk_dense_min(ctx: *const NwvCtx) -> usize;
+    pub fn nwv_bls_last_apk_dense(ctx: *mut NwvCtx, out: *mut u64) -> c_int;
     pub fn nwv_bls_last_keys(ctx: *mut NwvCtx, out: *mut u64) -> c_int;
     pub fn nwv_bls_set_msg_ring(ctx: *mut NwvCtx, slots: usize) -> c_int;
     pub fn nwv_bls_msg_ring(ctx: *const NwvCtx) -> usize;
