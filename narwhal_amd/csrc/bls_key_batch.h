@@ -124,11 +124,12 @@ inline void key_batch_plan(size_t n, const uint8_t* ok, const uint8_t* elig, con
     P.run = true;
 }
 
-// The per-item launches behind the check: need[i] != 0 marks an item that must run the per-item
-// kernel (an OK item outside the groups, an item of a rejected group).  A launch over a few items
+// The per-item launches behind this check and behind the wave batch check: need[i] != 0 marks an
+// item that must run the per-item kernel (an OK item outside the groups, an item of a rejected
+// group; the wave batch check marks every item of a rejected group).  A launch over a few items
 // costs one item's whole chain, so marked items less than `gap` items apart share one launch with
 // whatever lies between them.  Returns the half-open ranges, ascending.
-inline std::vector<std::pair<size_t, size_t>> key_batch_ranges(size_t n, const uint8_t* need, size_t gap) {
+inline std::vector<std::pair<size_t, size_t>> recheck_ranges(size_t n, const uint8_t* need, size_t gap) {
     std::vector<std::pair<size_t, size_t>> r;
     for (size_t i = 0; i < n; i++) {
         if (!need[i]) continue;
@@ -136,6 +137,10 @@ inline std::vector<std::pair<size_t, size_t>> key_batch_ranges(size_t n, const u
         else r.push_back({i, i + 1});
     }
     return r;
+}
+// the function's name while it served this check alone (host stubs built against that name still compile)
+inline std::vector<std::pair<size_t, size_t>> key_batch_ranges(size_t n, const uint8_t* need, size_t gap) {
+    return recheck_ranges(n, need, gap);
 }
 
 }  // namespace nwv

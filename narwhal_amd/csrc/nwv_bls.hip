@@ -1,21 +1,35 @@
 // nwv_bls.hip -- BLS12-381 min_sig verification engine on gfx950: the
 // kernels over bls_verify.h and the C ABI of include/nwv_bls.h.
 //
-// A call stages its inputs in one pinned arena and one H2D copy, then runs on three streams
-//   k_bls_keys_fill  one lane per key the device's key cache has not seen: decode + G2 membership
-//                    (psi(Q) = [x] Q), into the cache (fastcrypto validates a key once, at
-//                    deserialization); then k_bls_apk_g, one 8-lane group per item: the sum of the
-//                    item's keys (eight partial sums and a tree), its first bad key's status
-//   k_bls_sigs       one lane per item: decode + G1 membership (phi(P) = [-x^2] P)
-//   k_bls_h2c_g      one 8-lane group per item: H(msg) (RFC 9380 hash_to_curve G1), the two
-//                    field elements mapped side by side
-// joined by k_bls_status (the statuses in the oracle's order), then
-//   the pairing check, by default as ONE batch check over the call (bls_verify.h, kernels below:
-//     [r_i] H_i and [r_i] sig_i per item, S = sum [r_i] sig_i, every item's Miller loop and that
-//     of (-S, g2) in one grid, a product tree, one final exponentiation)
-//   and only when that rejects (or under NWV_FLAG_BLS_PER_ITEM)
-//     k_bls_pair   one lane per item: e(-sig, g2) e(H, apk) == 1 (two-pair Miller loop + final exp)
-// and copies the per-item statuses back.  The Miller loops are the hot part: Fp products on VALU
+// nwv_bls_verify_many runs on one lane of a device (verify_on): a plan made on the host (CallPlan:
+// the call's key table against the device's key cache, its ring slots, its path), the inputs staged
+// in one pinned arena and one H2D copy, then the path's function.  nwv_bls_last_path reports the
+// path's code:
+//   the small wave call (run_small, at most NWV_BLS_WAVE_MAX = 1,024 items; code 3), two streams:
+//     side 0  k_bls_keys_fill (keys the cache does not hold), then k_blsw_pre / k_blsw_pre_r: one
+//             wave per item hashes to G1 (or takes the message ring's point), one sums the keys
+//     main    k_blsw_sigdec, then the ahead hashes (k_blsw_h2c_ahead) and the aggregate-key fills
+//             (k_blsw_apk_fill) beside the pairing
+//     side 0  k_blsw_pair_sub: the pairing checks and the signatures' G1 checks in one launch,
+//             k_blsw_status; then the signature, message and aggregate-key rings' publishes
+//   the large wave call (run_large_wave), three streams:
+//     side 0  k_bls_keys_fill, then the key sums: k_blsw_apk, or the dense stage (k_blsd_total,
+//             k_blsd_apk, k_blsw_apk_list; nwv_bls_set_apk_dense_min)
+//     side 1  k_bls_h2c_2: hash to G1 on lane pairs
+//     main    k_bls_sigs (decode + G1 check, one lane per item), then one of three pairing stages
+//       the key-transposed check (pair_key_batch, nwv_bls_set_key_batch_min): code 6, or 7 when a
+//         group rejected and its items ran per item
+//       the wave batch check (pair_wave_batch, nwv_bls_set_wave_batch_min): one final
+//         exponentiation a group; code 4, or 5 when a group rejected
+//       per item (pair_per_item: k_blsw_pair_k, NWV_BLS_PACK items a wave): code 3
+//     and k_blsw_status
+//   the group engines (run_group: 8 lanes an item, the large calls' side streams with k_bls_apk_g):
+//     NWV_FLAG_BLS_PER_ITEM  k_bls_pair, one two-pair Miller loop + final exponentiation an item: code 0
+//     NWV_FLAG_BLS_BATCH     one random-linear-combination check over the call (k_bls_rlc_pts ..
+//                            k_bls_final): code 1; k_bls_pair only when it rejects: code 2
+// The statuses are the oracle's, in its order: signature decode, its G1 check (phi(P) = [-x^2] P),
+// the keys (fastcrypto validates a key once, at deserialization: psi(Q) = [x] Q), the pairing
+// equation e(-sig, g2) e(H, apk) == 1.  The Miller loops are the hot part: Fp products on VALU
 // v_mad_u64_u32 (bls381.h), no MFMA (no dense contraction).
 #include <hip/hip_runtime.h>
 
@@ -209,30 +223,12 @@ __global__ __launch_bounds__(BLS_LANES) void k_bls_apk_g(uint32_t n, KeyTab kt, 
     st_g2(out, x, y, inf);
     st_apk[i] = status;
 }
-// H(msg_i) on a group: lanes 0-3 map hash_to_field's u_0, lanes 4-7 u_1 (side by side), lane 4
-// hands its point to lane 0 through the group's LDS area, lane 0 adds and clears the cofactor
-// (kmode[i] = 1: item i's cofactor clearing is on its key side -- H0 = the maps' sum, see
-// k_bls_key_heff; kmode may be null)
-__global__ __launch_bounds__(BLS_LANES) void k_bls_h2c_g(uint32_t n, const uint8_t* msg, const uint64_t* off,
-                                                         const uint32_t* len, const uint8_t* dst, uint32_t dl,
-                                                         uint32_t* rec, const uint32_t* kmode) {
-    BLS_GIDX();
-    const jac<fp> q = h2c_map(msg + off[i], len[i], dst, dl, (g.slot & 4) ? 1 : 0);
-    g_sync();
-    if (g.slot == 4) st_g1j(g.xa, q);
-    g_sync();
-    const jac<fp> q1 = ld_g1j(g.xa);
-    if (g.slot != 0) return;
-    const jac<fp> h0 = jac_add(q, q1);
-    const jac<fp> h = kmode && kmode[i] ? h0 : jac_mul64(h0, BLS_H_EFF);
-    fp x = fp_zero(), y = fp_zero();
-    if (!h.inf) g1_to_affine_vt(x, y, h);
-    st_g1(rec + (size_t)G1_REC_WORDS * i, x, y, h.inf);
-}
-// The same on a lane pair: lane 2 j maps u_0 and lane 2 j + 1 u_1 of item 32 b + j; the odd lane
-// hands its point over through LDS.  32 items a wave instead of 8: a 16,384-item call is 512 waves
-// (one per SIMD at most) instead of 2,048 (two per SIMD, six of every group's eight lanes
-// repeating the pair's work), so each lane's dependent chain runs with its SIMD to itself.
+// H(msg_i) on a lane pair: lane 2 j maps u_0 and lane 2 j + 1 u_1 of item 32 b + j; the odd lane
+// hands its point over through LDS, the even lane adds and clears the cofactor (kmode[i] = 1: item
+// i's cofactor clearing is on its key side -- H0 = the maps' sum, see k_bls_key_heff; kmode may be
+// null).  32 items a wave instead of an 8-lane group's 8: a 16,384-item call is 512 waves (one per
+// SIMD at most) instead of 2,048 (two per SIMD, six of every group's eight lanes repeating the
+// pair's work), so each lane's dependent chain runs with its SIMD to itself.
 constexpr int G1J_WORDS = 3 * NL + 1;
 __global__ __launch_bounds__(BLS_LANES) void k_bls_h2c_2(uint32_t n, const uint8_t* msg, const uint64_t* off,
                                                          const uint32_t* len, const uint8_t* dst, uint32_t dl,
@@ -424,7 +420,7 @@ __global__ __launch_bounds__(64) void k_blsw_sub(uint32_t n, const uint32_t* rec
 }
 // e(-sig, g2) e(H, apk) == 1 for every item whose signature decoded and whose keys are valid
 // (run beside the signature's G1 check: the status join puts that check first)
-// H: homogeneous records (k_blsw_pre) or affine ones (k_bls_h2c_g, h_hom = 0); apk: Jacobian
+// H: homogeneous records (k_blsw_pre) or affine ones (k_bls_h2c_2, h_hom = 0); apk: Jacobian
 // records (k_blsw_apk)
 // (a one-key item whose key is in the cache takes the key's precomputed line table: the Miller
 // loop then only evaluates lines, no G2 arithmetic)
@@ -907,19 +903,6 @@ __global__ __launch_bounds__(64) void k_blsw_pair_sub(uint32_t n, const uint32_t
     else if (b < 2 * n)
         blsw_sub_item(wm, b - n, srec, st_dec, st_sub);
 }
-// the same with the pairing on the flat script (pair_flat, one item on the wave); NWV_BLS_SUB_FLAT=1
-__global__ __launch_bounds__(64) void k_blsw_pair_sub_f(uint32_t n, const uint32_t* srec, const int32_t* st_dec,
-                                                        const uint32_t* hrec, int h_hom, const uint32_t* arec,
-                                                        const int32_t* st_apk, KeyTab kt, const uint32_t* pk_off,
-                                                        const uint32_t* pk_cnt, const uint32_t* pk_idx,
-                                                        const uint32_t* kmode, int32_t* st_pair, int32_t* st_sub) {
-    BLSW_LDS(wave::NSLOTS_PAIR2);
-    const uint32_t b = blockIdx.x;
-    if (b < n)
-        pair_flat<8>(wm_lds, b, 1, srec, st_dec, hrec, h_hom, arec, st_apk, kt, pk_off, pk_cnt, pk_idx, kmode, st_pair);
-    else if (b < 2 * n)
-        blsw_sub_item(wm, b - n, srec, st_dec, st_sub);
-}
 // [h_eff] pk of newly registered keys (lane per key, affine records): the hash's cofactor clearing
 // moves onto the key side -- e(H0, [h_eff] pk) = e([h_eff] H0, pk) for H0 in E(Fp), as the
 // reduced pairing sees only H0's G1 component (tests/test_bls_hostemu.py
@@ -1260,6 +1243,60 @@ namespace {
         if (e_ != hipSuccess) return nwv_internal_set_err(NWV_ERR_HIP, hipGetErrorString(e_)); \
     } while (0)
 
+// an environment variable as a number clamped to [lo, hi] (unset: dflt; a negative value: lo)
+unsigned long env_ulong(const char* name, unsigned long dflt, unsigned long lo, unsigned long hi) {
+    const char* e = std::getenv(name);
+    if (!e) return dflt;
+    const unsigned long v = std::strtoul(e, nullptr, 10);
+    return std::strchr(e, '-') || v < lo ? lo : v > hi ? hi : v;
+}
+// the engine's environment, read once per process
+struct BlsEnv {
+    size_t wave_max = env_ulong("NWV_BLS_WAVE_MAX", 1024, 0, ~0ul);  // small wave calls: at most this many items
+    // items per group of the wave batch check
+    size_t wb_grp = env_ulong("NWV_BLS_BATCH_GROUP", NWV_BLS_BATCH_GROUP_DEFAULT, 1, 4096);
+    // the key-transposed batch check: groups of kb_grp eligible items, a group dropped when its
+    // distinct keys + 1 exceed 1 / kb_ratio of its items (0: never)
+    uint32_t kb_grp = (uint32_t)env_ulong("NWV_BLS_KEY_GROUP", NWV_BLS_KEY_GROUP_DEFAULT, 1, 65536);
+    uint32_t kb_ratio = (uint32_t)env_ulong("NWV_BLS_KEY_GROUP_RATIO", 4, 0, 1024);
+    unsigned long ad_forced = env_ulong("NWV_BLS_APK_LANES", 0, 0, ~0ul);  // lanes a dense item gets (4, 8, 16)
+    // items per pairing wave (1..4): one LDS bank of ~6.5 KB each
+    uint32_t pack = (uint32_t)env_ulong("NWV_BLS_PACK", 3, 1, BLS_PACK_MAX);
+    // diagnostic (occupancy experiments): bytes of extra LDS per pairing wave
+    size_t lds_pad = env_ulong("NWV_BLS_LDS_PAD", 0, 0, ~0ul);
+    // a call splits over the devices only into ranges of at least this many items
+    size_t shard_min = env_ulong("NWV_BLS_SHARD_MIN", 256, 0, ~0ul);
+    int replicas = (int)env_ulong("NWV_BLS_DEVICE_REPLICAS", 1, 1, 8);  // BlsDev shards per device (BlsCtx)
+};
+const BlsEnv& bls_env() {
+    static const BlsEnv e;
+    return e;
+}
+
+size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
+// A section of a staging arena or of a scratch buffer: declared once with its element type, it
+// gives the typed pointer into the host or the device copy of its buffer.
+template <class T>
+struct Sec {
+    size_t off = 0;
+    T* at(void* base) const { return reinterpret_cast<T*>(static_cast<uint8_t*>(base) + off); }
+};
+// sections of one buffer in order, each 256-byte aligned or packed behind the one before it
+struct Layout {
+    size_t end = 0;
+    template <class T>
+    Sec<T> packed(size_t bytes) {
+        const Sec<T> s{end};
+        end += bytes;
+        return s;
+    }
+    template <class T>
+    Sec<T> aligned(size_t bytes) {
+        end = al256(end);
+        return packed<T>(bytes);
+    }
+};
+
 struct DBuf {
     void* p = nullptr;
     size_t cap = 0;
@@ -1404,6 +1441,19 @@ struct BlsSigCache {
             next = (t + 1) % SC_CAP;
         }
         return NWV_OK;
+    }
+    // every one of the n signatures is in the ring: their slots -> pos (when given); the caller holds
+    // the lock, shared
+    bool holds_all(size_t n, const uint8_t* sigs48, uint32_t* pos = nullptr) const {
+        if (!rec.p || n > SC_CAP) return false;
+        Sig48 k;
+        for (size_t i = 0; i < n; i++) {
+            std::memcpy(k.b, sigs48 + 48 * i, 48);
+            const auto it = slot.find(k);
+            if (it == slot.end()) return false;
+            if (pos) pos[i] = it->second;
+        }
+        return true;
     }
     // the call's verified signatures (status OK) mapped to their slots (status null: the call
     // failed, its slots are only released)
@@ -1604,11 +1654,7 @@ int ctx_of(nwv_ctx* ctx, BlsCtx** out) {
     // engine's replicas, NWV_DEVICE_REPLICAS, are that engine's device objects, not devices)
     const int nd = nwv_internal_hip_device(ctx, -1);
     if (nd <= 0 || nwv_internal_hip_device(ctx, 0) < 0) return nwv_internal_set_err(NWV_ERR_NODEV, "context has no device");
-    static const int replicas = [] {
-        const char* e = std::getenv("NWV_BLS_DEVICE_REPLICAS");
-        const int r = e ? std::atoi(e) : 1;
-        return r < 1 ? 1 : (r > 8 ? 8 : r);
-    }();
+    const int replicas = bls_env().replicas;
     auto* c = new BlsCtx;
     for (int k = 0; k < nd; k++)
         for (int r = 0; r < replicas; r++) {
@@ -1642,6 +1688,15 @@ int dev_of(nwv_ctx* ctx, BlsDev** out) {
 // the device that served the calling thread's last nwv_bls_verify_many on a context (range 0's, when
 // the call split): what nwv_bls_last_kernel_ms / _last_path / _last_keys read; device 0 if none
 thread_local std::unordered_map<const nwv_ctx*, size_t> t_last_dev;
+// device object `device_index` of the context (the diagnostics' argument)
+int dev_at(nwv_ctx* ctx, int device_index, BlsCtx** c, BlsDev** out) {
+    int rc = ctx_of(ctx, c);
+    if (rc) return rc;
+    if (device_index < 0 || device_index >= (int)(*c)->devs.size())
+        return nwv_internal_set_err(NWV_ERR_ARG, "bad device index");
+    *out = (*c)->devs[device_index];
+    return NWV_OK;
+}
 int last_dev_of(nwv_ctx* ctx, BlsDev** out) {
     BlsCtx* c;
     int rc = ctx_of(ctx, &c);
@@ -1713,19 +1768,23 @@ struct Arena {
     std::vector<std::pair<const void*, size_t>> parts;
     std::vector<size_t> offs;
     size_t total = 0;
-    size_t add(const void* p, size_t n) {
-        const size_t o = total;
+    template <class T>
+    Sec<const T> add(const void* p, size_t n) {
+        const Sec<const T> s{total};
         parts.push_back({p, n});
-        offs.push_back(o);
-        total += (n + 255) & ~(size_t)255;
-        return o;
+        offs.push_back(total);
+        total += al256(n);
+        return s;
+    }
+    void fill(uint8_t* h) const {
+        for (size_t k = 0; k < parts.size(); k++)
+            if (parts[k].second) std::memcpy(h + offs[k], parts[k].first, parts[k].second);
     }
 };
 
 constexpr int kBlocks(size_t n) { return (int)((n + BLS_LANES - 1) / BLS_LANES); }
 // blocks of the group kernels: 8 items per 64-lane block
 constexpr int gBlocks(size_t n) { return (int)((n + BLS_LANES / GRP - 1) / (BLS_LANES / GRP)); }
-size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // Key registration: the keys the cache does not hold are decoded and subgroup-checked into a
 // scratch table, then (after the stream has completed) the valid ones are copied into fresh
@@ -1759,25 +1818,24 @@ int keycache_register(BlsDev& d, size_t n_keys, const uint8_t* keys) {
     const size_t m = fresh.size();
     if (m == 0) return NWV_OK;
     // scratch: keys, identity slot list, records, statuses; then the copy lists
-    const size_t o_keys = 0, o_slot = al256(96 * m), o_rec = al256(o_slot + 4 * m),
-                 o_st = al256(o_rec + 4 * G2_REC_WORDS * m), o_src = al256(o_st + 4 * m), o_dst = al256(o_src + 4 * m),
-                 o_end = o_dst + 4 * m;
-    if ((rc = lane->work.ensure(o_end)) || (rc = lane->stage.ensure(o_end))) return rc;
-    uint8_t* w = static_cast<uint8_t*>(lane->work.p);
-    uint8_t* h = static_cast<uint8_t*>(lane->stage.p);
-    std::memcpy(h + o_keys, fk.data(), 96 * m);
-    auto* hs = reinterpret_cast<uint32_t*>(h + o_slot);
-    for (size_t j = 0; j < m; j++) hs[j] = (uint32_t)j;
-    BLS_HIP(hipMemcpyAsync(w, h, o_rec, hipMemcpyHostToDevice, lane->stream));
-    hipLaunchKernelGGL(k_bls_keys_fill, dim3(kBlocks(m)), dim3(BLS_LANES), 0, lane->stream, (uint32_t)m, w + o_keys,
-                       reinterpret_cast<const uint32_t*>(w + o_slot), reinterpret_cast<uint32_t*>(w + o_rec),
-                       reinterpret_cast<int32_t*>(w + o_st));
+    Layout o;
+    const auto o_keys = o.aligned<uint8_t>(96 * m);
+    const auto o_slot = o.aligned<uint32_t>(4 * m), o_rec = o.aligned<uint32_t>(4 * G2_REC_WORDS * m);
+    const auto o_st = o.aligned<int32_t>(4 * m);
+    const auto o_src = o.aligned<uint32_t>(4 * m), o_dst = o.aligned<uint32_t>(4 * m);
+    if ((rc = lane->work.ensure(o.end)) || (rc = lane->stage.ensure(o.end))) return rc;
+    void* w = lane->work.p;
+    void* h = lane->stage.p;
+    std::memcpy(o_keys.at(h), fk.data(), 96 * m);
+    for (size_t j = 0; j < m; j++) o_slot.at(h)[j] = (uint32_t)j;
+    BLS_HIP(hipMemcpyAsync(w, h, o_rec.off, hipMemcpyHostToDevice, lane->stream));
+    hipLaunchKernelGGL(k_bls_keys_fill, dim3(kBlocks(m)), dim3(BLS_LANES), 0, lane->stream, (uint32_t)m, o_keys.at(w),
+                       o_slot.at(w), o_rec.at(w), o_st.at(w));
     BLS_HIP(hipGetLastError());
-    BLS_HIP(hipMemcpyAsync(h + o_st, w + o_st, 4 * m, hipMemcpyDeviceToHost, lane->stream));
+    BLS_HIP(hipMemcpyAsync(o_st.at(h), o_st.at(w), 4 * m, hipMemcpyDeviceToHost, lane->stream));
     BLS_HIP(hipStreamSynchronize(lane->stream));
-    const auto* kst = reinterpret_cast<const int32_t*>(h + o_st);
-    auto* src = reinterpret_cast<uint32_t*>(h + o_src);
-    auto* dst = reinterpret_cast<uint32_t*>(h + o_dst);
+    const int32_t* kst = o_st.at(h);
+    uint32_t *src = o_src.at(h), *dst = o_dst.at(h);
     size_t nv = 0;
     for (size_t j = 0; j < m && d.kc.used + nv < KC_CAP; j++)
         if (kst[j] == ST_OK) {
@@ -1786,11 +1844,10 @@ int keycache_register(BlsDev& d, size_t n_keys, const uint8_t* keys) {
             nv++;
         }
     if (nv == 0) return NWV_OK;
-    BLS_HIP(hipMemcpyAsync(w + o_src, h + o_src, o_end - o_src, hipMemcpyHostToDevice, lane->stream));
+    BLS_HIP(hipMemcpyAsync(o_src.at(w), src, o.end - o_src.off, hipMemcpyHostToDevice, lane->stream));
     hipLaunchKernelGGL(k_bls_rec_copy, dim3(kBlocks(nv * G2_REC_WORDS)), dim3(BLS_LANES), 0, lane->stream,
-                       (uint32_t)nv, reinterpret_cast<const uint32_t*>(w + o_src),
-                       reinterpret_cast<const uint32_t*>(w + o_dst), reinterpret_cast<const uint32_t*>(w + o_rec),
-                       static_cast<uint32_t*>(d.kc.rec.p), static_cast<int32_t*>(d.kc.st.p));
+                       (uint32_t)nv, o_src.at(w), o_dst.at(w), o_rec.at(w), static_cast<uint32_t*>(d.kc.rec.p),
+                       static_cast<int32_t*>(d.kc.st.p));
     BLS_HIP(hipGetLastError());
     // the new slots' Miller-loop line tables (the table grows by whole copies: registration is rare)
     const uint32_t need = d.kc.used + (uint32_t)nv;
@@ -1807,12 +1864,10 @@ int keycache_register(BlsDev& d, size_t n_keys, const uint8_t* keys) {
         std::swap(d.kc.lines.cap, nb.cap);
         d.kc.lines_slots = cap;
     }
-    hipLaunchKernelGGL(k_bls_key_heff, dim3(kBlocks(nv)), dim3(BLS_LANES), 0, lane->stream, (uint32_t)nv,
-                       reinterpret_cast<const uint32_t*>(w + o_dst), static_cast<const uint32_t*>(d.kc.rec.p),
-                       static_cast<uint32_t*>(d.kc.hrec.p));
-    hipLaunchKernelGGL(k_blsw_key_lines, dim3((unsigned)nv), dim3(64), 0, lane->stream, (uint32_t)nv,
-                       reinterpret_cast<const uint32_t*>(w + o_dst), static_cast<const uint32_t*>(d.kc.hrec.p),
-                       static_cast<uint32_t*>(d.kc.lines.p));
+    hipLaunchKernelGGL(k_bls_key_heff, dim3(kBlocks(nv)), dim3(BLS_LANES), 0, lane->stream, (uint32_t)nv, o_dst.at(w),
+                       static_cast<const uint32_t*>(d.kc.rec.p), static_cast<uint32_t*>(d.kc.hrec.p));
+    hipLaunchKernelGGL(k_blsw_key_lines, dim3((unsigned)nv), dim3(64), 0, lane->stream, (uint32_t)nv, o_dst.at(w),
+                       static_cast<const uint32_t*>(d.kc.hrec.p), static_cast<uint32_t*>(d.kc.lines.p));
     BLS_HIP(hipGetLastError());
     BLS_HIP(hipStreamSynchronize(lane->stream));
     for (size_t k = 0; k < nv; k++) d.kc.slot.emplace(fresh[src[k]], dst[k]);  // published after the copy
@@ -1820,773 +1875,853 @@ int keycache_register(BlsDev& d, size_t n_keys, const uint8_t* keys) {
     return NWV_OK;
 }
 
-// the whole verify_many pipeline on one lane of a device: after one H2D copy, three streams --
-//   side 0: the call's keys the cache does not hold, decoded into the scratch table
-//           (k_bls_keys_fill), then the key sums (k_bls_apk_g)
-//   main  : signature decode + G1 checks (k_bls_sigs)
-//   side 1: hash to G1 (k_bls_h2c_g)
-// -- then, joined on the main stream, the statuses in the oracle's order and the pairing check
-int verify_on(BlsDev& d, size_t n_keys, const uint8_t* keys, size_t n, const uint8_t* sigs, const uint32_t* pk_off,
-              const uint32_t* pk_cnt, const uint32_t* pk_idx, size_t n_idx, const uint8_t* msg_base,
-              const uint64_t* msg_off, const uint32_t* msg_len, size_t msg_bytes, const uint8_t* dst, size_t dl,
-              int32_t* status, const Ahead* ahead = nullptr, uint64_t* mstat = nullptr, uint64_t* astat = nullptr,
-              bool latency = false) {
-    LaneLease lane(d, latency);
-    if (lane.rc()) return lane.rc();
-    BlsLane& L = *lane;
-    static const uint8_t zero[8] = {0};
+// ---- nwv_bls_verify_many on one device lane: a plan made on the host, typed buffers, one
+// function per path (the file's header names the paths)
+//
+// what a call brings (a range of a split call brings its own extents)
+struct CallIn {
+    size_t n_keys;
+    const uint8_t* keys;
+    size_t n;
+    const uint8_t* sigs;
+    const uint32_t *pk_off, *pk_cnt, *pk_idx;
+    size_t n_idx;  // entries of pk_idx the call's items reach
+    const uint8_t* msg_base;
+    const uint64_t* msg_off;
+    const uint32_t* msg_len;
+    size_t msg_bytes;
+    const uint8_t* dst;
+    size_t dl;
+};
+// a call's ring slots.  The order is a condition: verify_on declares its LaneLease, then its shared
+// lock on the key cache, then this, so the slots are given back (ApkSlots, MsgSlots, SigSlots, each
+// after its streams' waits) before the key-cache lock drops and before the lane returns to the pool
+struct CallSlots {
+    SigSlots kept;
+    MsgSlots ms;
+    ApkSlots as;
+};
+// everything a call decides on the host, before any GPU work
+struct CallPlan {
     // pairing-check mode: the wave engine per item (default), or the 8-lane group kernels -- one
     // random-linear-combination batch check (NWV_FLAG_BLS_BATCH) or per item (NWV_FLAG_BLS_PER_ITEM)
-    const bool group_item = (d.flags & NWV_FLAG_BLS_PER_ITEM) != 0;
-    const bool batch = !group_item && (d.flags & NWV_FLAG_BLS_BATCH) != 0;
-    const bool wavem = !group_item && !batch;
-    // wave-per-item hashing and G1 checks while the call has fewer items than the chip has SIMDs
-    // (latency); above that, one item per lane keeps every lane busy (throughput)
-    static const size_t wave_max = [] {
-        const char* e = std::getenv("NWV_BLS_WAVE_MAX");
-        return e ? (size_t)std::strtoul(e, nullptr, 10) : (size_t)1024;
-    }();
-    const bool wave_small = wavem && n <= wave_max;
-    // the wave batch check (one final exponentiation per group of wb_grp items): large wave calls
-    // of at least nwv_bls_set_wave_batch_min items
-    static const size_t wb_grp = [] {
-        const char* e = std::getenv("NWV_BLS_BATCH_GROUP");
-        const size_t v = e ? (size_t)std::strtoul(e, nullptr, 10) : (size_t)NWV_BLS_BATCH_GROUP_DEFAULT;
-        return v < 1 ? (size_t)1 : v > 4096 ? (size_t)4096 : v;
-    }();
-    const size_t wb_min = d.wave_batch_min.load(std::memory_order_relaxed);
-    const bool wbatch = wavem && !wave_small && wb_min > 0 && n >= wb_min;
-    const size_t wb_ng = wbatch ? (n + wb_grp - 1) / wb_grp : 0, wb_m = wbatch ? n + wb_ng : 0;
-    // the key-transposed batch check (bls_key_batch.h): large wave calls of at least
-    // nwv_bls_set_key_batch_min items; groups of kb_grp eligible items, a group dropped when its
-    // distinct keys + 1 exceed 1 / kb_ratio of its items (0: never)
-    static const uint32_t kb_grp = [] {
-        const char* e = std::getenv("NWV_BLS_KEY_GROUP");
-        const unsigned long v = e ? std::strtoul(e, nullptr, 10) : (unsigned long)NWV_BLS_KEY_GROUP_DEFAULT;
-        return (uint32_t)(v < 1 ? 1 : v > 65536 ? 65536 : v);
-    }();
-    static const uint32_t kb_ratio = [] {
-        const char* e = std::getenv("NWV_BLS_KEY_GROUP_RATIO");
-        const unsigned long v = e ? std::strtoul(e, nullptr, 10) : 4ul;
-        return (uint32_t)(v > 1024 ? 1024 : v);
-    }();
-    const size_t kb_min = d.key_batch_min.load(std::memory_order_relaxed);
-    // the dense key-sum stage (bls_apk_dense.h): large wave calls of at least
-    // nwv_bls_set_apk_dense_min items; NWV_BLS_APK_LANES forces the lanes an item gets (4, 8, 16)
-    static const unsigned long ad_forced = [] {
-        const char* e = std::getenv("NWV_BLS_APK_LANES");
-        return e ? std::strtoul(e, nullptr, 10) : 0ul;
-    }();
-    const size_t ad_min = d.apk_dense_min.load(std::memory_order_relaxed);
-    const bool ad_run = wavem && !wave_small && ad_min > 0 && n >= ad_min;
-    int rc;
-    // the call's key table: cache slots (lookups only) or scratch entries KC_CAP + j
-    std::shared_lock<std::shared_mutex> kc_hold(d.kc.mu);  // records stay put while our kernels read them
-    const bool cached = !(d.flags & NWV_FLAG_NO_KEYCACHE) && d.kc.rec.p != nullptr;
-    std::vector<uint32_t> ktab(n_keys), fill_slot;
+    bool group_item = false, batch = false, wavem = false;
+    bool wave_small = false;  // at most NWV_BLS_WAVE_MAX items: the two-stream call
+    bool wbatch = false;      // the wave batch check: wb_ng groups, wb_m Miller entries
+    bool kb_cand = false;     // the key-transposed batch check, if its plan runs
+    bool ad_run = false;      // the dense key-sum stage
+    bool keep = false, use_ring = false, use_apk = false;  // the signature, message and aggregate-key rings
+    bool cached = false, kside = false;
+    bool no_timing = false;
+    size_t wb_ng = 0, wb_m = 0;
+    // the key table: cache slots (lookups only) or scratch entries KC_CAP + j
+    std::vector<uint32_t> ktab, fill_slot, remap, kmode;
     std::vector<uint8_t> fill_keys;
     uint64_t hits = 0;
-    {
-        std::unordered_map<std::string, uint32_t> fresh;
-        for (size_t j = 0; j < n_keys; j++) {
-            std::string kb(reinterpret_cast<const char*>(keys + 96 * j), 96);
-            if (cached) {
-                auto it = d.kc.slot.find(kb);
-                if (it != d.kc.slot.end()) {
-                    ktab[j] = it->second;
-                    hits++;
-                    continue;
-                }
-            }
-            auto f = fresh.find(kb);
-            if (f != fresh.end()) {
-                ktab[j] = KC_CAP + f->second;
+    size_t n_dec() const { return fill_slot.size(); }  // keys decoded by this call
+    // the dense key-sum stage's item lists and lanes
+    nwv::ApkDenseSplit ads;
+    uint32_t ad_lanes = 0;
+    // the message ring's arena section: aoff | hsrc | hpub | aslot | alen | ahead messages
+    std::vector<uint8_t> rsec;
+    size_t n_ah = 0, r_hsrc = 0, r_hpub = 0, r_aslot = 0, r_alen = 0, r_amsg = 0;
+    uint64_t mcount[5] = {0, 0, 0, 0, 0};
+    // the aggregate-key ring: the call's own key lists when some item hit (a_fill: the fills' items,
+    // then their slots)
+    std::vector<uint32_t> a_off, a_cnt, a_idx, a_fill;
+    size_t n_fill = 0;
+    uint64_t acount[4] = {0, 0, 0, 0};
+    // the key lists the kernels read
+    const uint32_t *k_off = nullptr, *k_cnt = nullptr;
+    const std::vector<uint32_t>* k_idx = nullptr;
+};
+// stage times of the completed call, its path and counters -> the device's "last call"
+struct CallStats {
+    int path = 0;
+    bool untimed = false;  // a small call that recorded no stage events
+    uint64_t wb[3] = {0, 0, 0}, kb[5] = {0, 0, 0, 0, 0}, ad[4] = {0, 0, 0, 0};
+};
+
+// the call's key table, its remapped key lists and the key-side flags (under the caller's shared
+// lock on the cache)
+void plan_keys(const BlsKeyCache& kc, const CallIn& c, CallPlan& P) {
+    P.ktab.resize(c.n_keys);
+    std::unordered_map<std::string, uint32_t> fresh;
+    for (size_t j = 0; j < c.n_keys; j++) {
+        std::string kb(reinterpret_cast<const char*>(c.keys + 96 * j), 96);
+        if (P.cached) {
+            auto it = kc.slot.find(kb);
+            if (it != kc.slot.end()) {
+                P.ktab[j] = it->second;
+                P.hits++;
                 continue;
             }
-            const uint32_t e = (uint32_t)fresh.size();
-            fresh.emplace(std::move(kb), e);
-            ktab[j] = KC_CAP + e;
-            fill_slot.push_back(e);
-            fill_keys.insert(fill_keys.end(), keys + 96 * j, keys + 96 * (j + 1));
         }
+        auto f = fresh.find(kb);
+        if (f != fresh.end()) {
+            P.ktab[j] = KC_CAP + f->second;
+            continue;
+        }
+        const uint32_t e = (uint32_t)fresh.size();
+        fresh.emplace(std::move(kb), e);
+        P.ktab[j] = KC_CAP + e;
+        P.fill_slot.push_back(e);
+        P.fill_keys.insert(P.fill_keys.end(), c.keys + 96 * j, c.keys + 96 * (j + 1));
     }
-    std::vector<uint32_t> remap(n_idx);
-    for (size_t t = 0; t < n_idx; t++) remap[t] = ktab[pk_idx[t]];
+    P.remap.resize(c.n_idx);
+    for (size_t t = 0; t < c.n_idx; t++) P.remap[t] = P.ktab[c.pk_idx[t]];
     // key-side cofactor clearing (wave path): items whose keys are all in the cache use the keys'
     // [h_eff] pk records and line tables, and their hash skips the h_eff chain
-    const bool kside = wavem && cached && d.kc.lines_slots;
-    std::vector<uint32_t> kmode(kside ? n : 0);
-    for (size_t i = 0; i < kmode.size(); i++) {
-        bool all = pk_cnt[i] > 0;
-        for (uint32_t j = 0; j < pk_cnt[i] && all; j++) all = remap[pk_off[i] + j] < KC_CAP;
-        kmode[i] = all ? 1u : 0u;
+    P.kside = P.wavem && P.cached && kc.lines_slots;
+    P.kmode.resize(P.kside ? c.n : 0);
+    for (size_t i = 0; i < P.kmode.size(); i++) {
+        bool all = c.pk_cnt[i] > 0;
+        for (uint32_t j = 0; j < c.pk_cnt[i] && all; j++) all = P.remap[c.pk_off[i] + j] < KC_CAP;
+        P.kmode[i] = all ? 1u : 0u;
     }
-    // the dense key-sum stage's item lists and lanes (the stage reads the caller's key numbers and
-    // the key table itself: an ascending list is ascending in those, not in cache slots)
-    nwv::ApkDenseSplit ads;
-    if (ad_run) nwv::apk_dense_split(n, kside ? kmode.data() : nullptr, pk_cnt, ads);
-    const size_t n_dn = ads.dense.size(), n_rest = ads.rest.size();
-    const uint32_t ad_lanes = ad_run ? nwv::apk_dense_lanes(n_dn, ad_forced) : 0;
-    const size_t n_dec = fill_slot.size();  // keys decoded by this call
+}
+
+// messages to hash ahead of need, packed for k_blsw_h2c_ahead: offsets | slots | lengths | bytes
+struct AheadPack {
+    std::vector<uint32_t> slot, len;
+    std::vector<uint64_t> off;
+    std::vector<uint8_t> msg;
+    size_t n() const { return slot.size(); }
+    void push(uint32_t ring_slot, const uint8_t* m, uint32_t l) {
+        slot.push_back(ring_slot);
+        len.push_back(l);
+        off.push_back(msg.size());
+        msg.insert(msg.end(), m, m + l);
+    }
+    void write(void* o_off, void* o_slot, void* o_len, void* o_msg) const {
+        if (!n()) return;
+        std::memcpy(o_off, off.data(), 8 * n());
+        std::memcpy(o_slot, slot.data(), 4 * n());
+        std::memcpy(o_len, len.data(), 4 * n());
+        if (!msg.empty()) std::memcpy(o_msg, msg.data(), msg.size());
+    }
+};
+void launch_ahead(hipStream_t s, size_t n, const uint8_t* msg, const uint64_t* off, const uint32_t* len,
+                  const uint8_t* dst, size_t dl, void* ring_rec, const uint32_t* slot) {
+    hipLaunchKernelGGL(k_blsw_h2c_ahead, dim3((unsigned)n), dim3(64), 0, s, (uint32_t)n, msg, off, len, dst,
+                       (uint32_t)dl, static_cast<uint32_t*>(ring_rec), slot);
+}
+
+// the device's message ring (small wave calls): hits pinned, one slot reserved per distinct missing
+// message and per ahead message that is neither cached nor a duplicate
+void plan_msg_ring(nwv::BlsMsgRing& R, const CallIn& c, const Ahead* ahead, MsgSlots& ms, CallPlan& P) {
+    const size_t n = c.n;
+    std::vector<uint32_t> hsrc(n, MR_NONE), hpub(n, MR_NONE);
+    std::unordered_multimap<uint64_t, size_t> mine;  // this call's reserved keys: hash -> ms.fresh index
+    auto mine_has = [&](const nwv::MsgKey& k, uint64_t hk) {
+        const auto r = mine.equal_range(hk);
+        for (auto it = r.first; it != r.second; ++it)
+            if (ms.fresh[it->second].key == k) return true;
+        return false;
+    };
+    auto take = [&](const nwv::MsgKey& k, uint32_t gate, bool is_ahead) {
+        const uint64_t hk = k.hash();
+        if (mine_has(k, hk)) return MR_NONE;
+        const uint32_t r = R.reserve();
+        if (r == nwv::BlsMsgRing::NONE) return MR_NONE;  // every slot in use: computed, not kept
+        mine.emplace(hk, ms.fresh.size());
+        ms.fresh.push_back({r, k, gate, is_ahead});
+        return r;
+    };
+    for (size_t i = 0; i < n; i++) {
+        P.mcount[2]++;
+        if (c.msg_len[i] > nwv::MsgKey::MAX_MSG) continue;
+        const nwv::MsgKey k = nwv::MsgKey::make(c.dst, c.dl, c.msg_base + c.msg_off[i], c.msg_len[i]);
+        const uint32_t s = R.lookup_pin(k);
+        if (s != nwv::BlsMsgRing::NONE) {
+            hsrc[i] = s;
+            ms.pinned.push_back(s);
+            P.mcount[2]--;
+            P.mcount[P.kside && P.kmode[i] ? 0 : 1]++;
+            continue;
+        }
+        hpub[i] = take(k, UINT32_MAX, false);
+    }
+    AheadPack ap;
+    for (size_t j = 0; ahead && j < ahead->n; j++) {
+        if (ahead->len[j] > nwv::MsgKey::MAX_MSG) continue;
+        const nwv::MsgKey k = nwv::MsgKey::make(c.dst, c.dl, ahead->base + ahead->off[j], ahead->len[j]);
+        if (R.contains(k)) continue;
+        const uint32_t r = take(k, ahead->gate ? ahead->gate[j] : UINT32_MAX, true);
+        if (r != MR_NONE) ap.push(r, ahead->base + ahead->off[j], ahead->len[j]);
+    }
+    P.n_ah = ap.n();
+    P.r_hsrc = 8 * P.n_ah;
+    P.r_hpub = P.r_hsrc + 4 * n;
+    P.r_aslot = P.r_hpub + 4 * n;
+    P.r_alen = P.r_aslot + 4 * P.n_ah;
+    P.r_amsg = P.r_alen + 4 * P.n_ah;
+    P.rsec.assign(P.r_amsg + ap.msg.size() + 1, 0);
+    uint8_t* r = P.rsec.data();
+    ap.write(r, r + P.r_aslot, r + P.r_alen, r + P.r_amsg);
+    std::memcpy(r + P.r_hsrc, hsrc.data(), 4 * n);
+    std::memcpy(r + P.r_hpub, hpub.data(), 4 * n);
+}
+
+// the device's aggregate-key ring (small wave calls): the key-side items of 2 to 1,024 keys.  A hit
+// is pinned and its item becomes a one-key item on the ring slot, in arrays of the call's own (made
+// only when some item hit); a set missed for the second time reserves a slot for k_blsw_apk_fill
+// (one item of the call per set)
+void plan_apk_ring(nwv::BlsApkRing& R, const CallIn& c, ApkSlots& as, CallPlan& P) {
+    const size_t n = c.n;
+    std::vector<uint32_t> hit(n, nwv::BlsApkRing::NONE);
+    for (size_t i = 0; i < n; i++) {
+        if (!P.kmode[i] || !nwv::ApkKey::eligible(c.pk_cnt[i])) continue;
+        nwv::ApkKey k = nwv::ApkKey::make(P.remap.data() + c.pk_off[i], c.pk_cnt[i]);
+        const uint32_t s = R.lookup_pin(k);
+        if (s != nwv::BlsApkRing::NONE) {
+            hit[i] = s;
+            as.pinned.push_back(s);
+            P.acount[0]++;
+            continue;
+        }
+        P.acount[1]++;
+        bool mine = false;  // an earlier item of this call fills the set already
+        for (const ApkSlots::Fresh& f : as.fresh) mine = mine || f.key == k;
+        if (mine) continue;
+        bool noted = false;
+        const uint32_t r = R.miss(k, &noted);
+        if (noted) P.acount[2]++;
+        if (r != nwv::BlsApkRing::NONE) as.fresh.push_back({r, (uint32_t)i, std::move(k)});
+    }
+    if (P.acount[0]) {
+        P.a_off.assign(c.pk_off, c.pk_off + n);
+        P.a_cnt.assign(c.pk_cnt, c.pk_cnt + n);
+        P.a_idx = P.remap;
+        for (size_t i = 0; i < n; i++) {
+            if (hit[i] == nwv::BlsApkRing::NONE) continue;
+            P.a_off[i] = (uint32_t)P.a_idx.size();
+            P.a_cnt[i] = 1;
+            P.a_idx.push_back(AR_BASE + hit[i]);
+        }
+    }
+    for (const ApkSlots::Fresh& f : as.fresh) P.a_fill.push_back(f.item);
+    for (const ApkSlots::Fresh& f : as.fresh) P.a_fill.push_back(f.slot);
+    P.n_fill = as.fresh.size();
+}
+
+// the whole plan.  It reserves and pins ring slots (S gives them back) and reads the key cache, so
+// the caller holds its lane and the cache's shared lock
+int plan_call(BlsDev& d, BlsLane& L, const CallIn& c, const Ahead* ahead, CallSlots& S, CallPlan& P) {
+    const BlsEnv& env = bls_env();
+    const size_t n = c.n;
+    P.group_item = (d.flags & NWV_FLAG_BLS_PER_ITEM) != 0;
+    P.batch = !P.group_item && (d.flags & NWV_FLAG_BLS_BATCH) != 0;
+    P.wavem = !P.group_item && !P.batch;
+    // wave-per-item hashing and G1 checks while the call has fewer items than the chip has SIMDs
+    // (latency); above that, one item per lane keeps every lane busy (throughput)
+    P.wave_small = P.wavem && n <= env.wave_max;
+    // the wave batch check (one final exponentiation per group of wb_grp items): large wave calls
+    // of at least nwv_bls_set_wave_batch_min items
+    const size_t wb_min = d.wave_batch_min.load(std::memory_order_relaxed);
+    P.wbatch = P.wavem && !P.wave_small && wb_min > 0 && n >= wb_min;
+    P.wb_ng = P.wbatch ? (n + env.wb_grp - 1) / env.wb_grp : 0;
+    P.wb_m = P.wbatch ? n + P.wb_ng : 0;
+    // the dense key-sum stage (bls_apk_dense.h): large wave calls of at least
+    // nwv_bls_set_apk_dense_min items; NWV_BLS_APK_LANES forces the lanes an item gets (4, 8, 16)
+    const size_t ad_min = d.apk_dense_min.load(std::memory_order_relaxed);
+    P.ad_run = P.wavem && !P.wave_small && ad_min > 0 && n >= ad_min;
+    P.cached = !(d.flags & NWV_FLAG_NO_KEYCACHE) && d.kc.rec.p != nullptr;
+    plan_keys(d.kc, c, P);
+    // the key-transposed batch check (bls_key_batch.h): large wave calls of at least
+    // nwv_bls_set_key_batch_min items (every item's keys cached is what the key side already asks)
+    const size_t kb_min = d.key_batch_min.load(std::memory_order_relaxed);
+    P.kb_cand = P.wavem && !P.wave_small && P.kside && kb_min > 0 && n >= kb_min;
+    // (the dense stage reads the caller's key numbers and the key table itself: an ascending list is
+    // ascending in those, not in cache slots)
+    if (P.ad_run) nwv::apk_dense_split(n, P.kside ? P.kmode.data() : nullptr, c.pk_cnt, P.ads);
+    P.ad_lanes = P.ad_run ? nwv::apk_dense_lanes(P.ads.dense.size(), env.ad_forced) : 0;
     // verified signatures stay decoded in the device's ring (BlsSigCache) for aggregates
     // (n <= 1,024 whatever NWV_BLS_WAVE_MAX says: the calls in flight on a device's lanes then hold
     // at most kMaxBusySlots busy slots)
-    const bool keep = wave_small && n <= 1024 && !(d.flags & NWV_FLAG_NO_SIGCACHE);
-    SigSlots kept;
-    if (keep) {
-        if ((rc = d.sc.reserve(n, kept.slots))) return rc;
-        kept.sc = &d.sc;
-        kept.n = n;
+    P.keep = P.wave_small && n <= 1024 && !(d.flags & NWV_FLAG_NO_SIGCACHE);
+    if (P.keep) {
+        int rc = d.sc.reserve(n, S.kept.slots);
+        if (rc) return rc;
+        S.kept.sc = &d.sc;
+        S.kept.n = n;
     }
-    // the device's message ring (the same small wave calls): hits pinned, one slot reserved per
-    // distinct missing message and per ahead message that is neither cached nor a duplicate
-    const bool use_ring = wave_small && n <= 1024 && d.mr.on.load(std::memory_order_acquire) &&
-                          dl <= nwv::MsgKey::MAX_DST;
-    MsgSlots ms;
-    std::vector<uint8_t> rsec;  // the ring's arena section: aoff | hsrc | hpub | aslot | alen | ahead messages
-    size_t n_ah = 0, r_hsrc = 0, r_hpub = 0, r_aslot = 0, r_alen = 0, r_amsg = 0;
-    uint64_t mcount[5] = {0, 0, 0, 0, 0};
-    if (use_ring) {
-        nwv::BlsMsgRing& R = d.mr.ring;
-        ms.ring = &R;
-        ms.streams[0] = L.stream;
-        ms.streams[1] = L.side[0];
-        std::vector<uint32_t> hsrc(n, MR_NONE), hpub(n, MR_NONE);
-        std::unordered_multimap<uint64_t, size_t> mine;  // this call's reserved keys: hash -> ms.fresh index
-        auto mine_has = [&](const nwv::MsgKey& k, uint64_t hk) {
-            const auto r = mine.equal_range(hk);
-            for (auto it = r.first; it != r.second; ++it)
-                if (ms.fresh[it->second].key == k) return true;
-            return false;
-        };
-        auto take = [&](const nwv::MsgKey& k, uint32_t gate, bool is_ahead) {
-            const uint64_t hk = k.hash();
-            if (mine_has(k, hk)) return MR_NONE;
-            const uint32_t r = R.reserve();
-            if (r == nwv::BlsMsgRing::NONE) return MR_NONE;  // every slot in use: computed, not kept
-            mine.emplace(hk, ms.fresh.size());
-            ms.fresh.push_back({r, k, gate, is_ahead});
-            return r;
-        };
-        for (size_t i = 0; i < n; i++) {
-            mcount[2]++;
-            if (msg_len[i] > nwv::MsgKey::MAX_MSG) continue;
-            const nwv::MsgKey k = nwv::MsgKey::make(dst, dl, msg_base + msg_off[i], msg_len[i]);
-            const uint32_t s = R.lookup_pin(k);
-            if (s != nwv::BlsMsgRing::NONE) {
-                hsrc[i] = s;
-                ms.pinned.push_back(s);
-                mcount[2]--;
-                mcount[kside && kmode[i] ? 0 : 1]++;
-                continue;
-            }
-            hpub[i] = take(k, UINT32_MAX, false);
-        }
-        std::vector<uint32_t> aslot, alen;
-        std::vector<uint64_t> aoff;
-        std::vector<uint8_t> amsg;
-        for (size_t j = 0; ahead && j < ahead->n; j++) {
-            if (ahead->len[j] > nwv::MsgKey::MAX_MSG) continue;
-            const nwv::MsgKey k = nwv::MsgKey::make(dst, dl, ahead->base + ahead->off[j], ahead->len[j]);
-            if (R.contains(k)) continue;
-            const uint32_t r = take(k, ahead->gate ? ahead->gate[j] : UINT32_MAX, true);
-            if (r == MR_NONE) continue;
-            aslot.push_back(r);
-            alen.push_back(ahead->len[j]);
-            aoff.push_back(amsg.size());
-            amsg.insert(amsg.end(), ahead->base + ahead->off[j], ahead->base + ahead->off[j] + ahead->len[j]);
-        }
-        n_ah = aslot.size();
-        r_hsrc = 8 * n_ah;
-        r_hpub = r_hsrc + 4 * n;
-        r_aslot = r_hpub + 4 * n;
-        r_alen = r_aslot + 4 * n_ah;
-        r_amsg = r_alen + 4 * n_ah;
-        rsec.assign(r_amsg + amsg.size() + 1, 0);
-        if (n_ah) {
-            std::memcpy(rsec.data(), aoff.data(), 8 * n_ah);
-            std::memcpy(rsec.data() + r_aslot, aslot.data(), 4 * n_ah);
-            std::memcpy(rsec.data() + r_alen, alen.data(), 4 * n_ah);
-            if (!amsg.empty()) std::memcpy(rsec.data() + r_amsg, amsg.data(), amsg.size());
-        }
-        std::memcpy(rsec.data() + r_hsrc, hsrc.data(), 4 * n);
-        std::memcpy(rsec.data() + r_hpub, hpub.data(), 4 * n);
+    P.use_ring = P.wave_small && n <= 1024 && d.mr.on.load(std::memory_order_acquire) && c.dl <= nwv::MsgKey::MAX_DST;
+    if (P.use_ring) {
+        S.ms.ring = &d.mr.ring;
+        S.ms.streams[0] = L.stream;
+        S.ms.streams[1] = L.side[0];
+        plan_msg_ring(d.mr.ring, c, ahead, S.ms, P);
     }
-    // the device's aggregate-key ring (the same small wave calls): the key-side items of 2 to 1,024
-    // keys.  A hit is pinned and its item becomes a one-key item on the ring slot, in arrays of the
-    // call's own (made only when some item hit); a set missed for the second time reserves a slot
-    // for k_blsw_apk_fill (one item of the call per set)
-    const bool use_apk = wave_small && n <= 1024 && kside && d.ar.on.load(std::memory_order_acquire);
-    ApkSlots as;
-    std::vector<uint32_t> a_off, a_cnt, a_idx, a_fill;  // a_fill: the fills' items, then their slots
-    uint64_t acount[4] = {0, 0, 0, 0};
-    if (use_apk) {
-        nwv::BlsApkRing& R = d.ar.ring;
-        as.ring = &R;
-        as.streams[0] = L.stream;
-        as.streams[1] = L.side[0];
-        std::vector<uint32_t> hit(n, nwv::BlsApkRing::NONE);
-        for (size_t i = 0; i < n; i++) {
-            if (!kmode[i] || !nwv::ApkKey::eligible(pk_cnt[i])) continue;
-            nwv::ApkKey k = nwv::ApkKey::make(remap.data() + pk_off[i], pk_cnt[i]);
-            const uint32_t s = R.lookup_pin(k);
-            if (s != nwv::BlsApkRing::NONE) {
-                hit[i] = s;
-                as.pinned.push_back(s);
-                acount[0]++;
-                continue;
-            }
-            acount[1]++;
-            bool mine = false;  // an earlier item of this call fills the set already
-            for (const ApkSlots::Fresh& f : as.fresh) mine = mine || f.key == k;
-            if (mine) continue;
-            bool noted = false;
-            const uint32_t r = R.miss(k, &noted);
-            if (noted) acount[2]++;
-            if (r != nwv::BlsApkRing::NONE) as.fresh.push_back({r, (uint32_t)i, std::move(k)});
-        }
-        if (acount[0]) {
-            a_off.assign(pk_off, pk_off + n);
-            a_cnt.assign(pk_cnt, pk_cnt + n);
-            a_idx = remap;
-            for (size_t i = 0; i < n; i++) {
-                if (hit[i] == nwv::BlsApkRing::NONE) continue;
-                a_off[i] = (uint32_t)a_idx.size();
-                a_cnt[i] = 1;
-                a_idx.push_back(AR_BASE + hit[i]);
-            }
-        }
-        for (const ApkSlots::Fresh& f : as.fresh) a_fill.push_back(f.item);
-        for (const ApkSlots::Fresh& f : as.fresh) a_fill.push_back(f.slot);
+    P.use_apk = P.wave_small && n <= 1024 && P.kside && d.ar.on.load(std::memory_order_acquire);
+    if (P.use_apk) {
+        S.as.ring = &d.ar.ring;
+        S.as.streams[0] = L.stream;
+        S.as.streams[1] = L.side[0];
+        plan_apk_ring(d.ar.ring, c, S.as, P);
     }
-    const size_t n_fill = as.fresh.size();
-    const bool a_hit = !a_idx.empty();
-    const uint32_t* k_off = a_hit ? a_off.data() : pk_off;
-    const uint32_t* k_cnt = a_hit ? a_cnt.data() : pk_cnt;
-    const std::vector<uint32_t>& k_idx = a_hit ? a_idx : remap;
-    const size_t nk_idx = k_idx.size();
-    uint8_t seed[32];
-    nwv_internal_fill_seed(nullptr, seed);  // the batch coefficients' key: OS entropy per call
-    Arena a;
-    const size_t o_keys = a.add(n_dec ? (const void*)fill_keys.data() : zero, 96 * n_dec + 8),
-                 o_kslot = a.add(n_dec ? (const void*)fill_slot.data() : zero, 4 * n_dec + 4),
-                 o_sigs = a.add(sigs, 48 * n), o_off = a.add(k_off, 4 * n), o_cnt = a.add(k_cnt, 4 * n),
-                 o_idx = a.add(nk_idx ? (const void*)k_idx.data() : zero, 4 * nk_idx + 4),
-                 o_msg = a.add(msg_bytes ? (const void*)msg_base : zero, msg_bytes + 1),
-                 o_moff = a.add(msg_off, 8 * n), o_mlen = a.add(msg_len, 4 * n), o_dst = a.add(dst, dl),
-                 o_seed = a.add(seed, 32), o_kmode = a.add(kside ? (const void*)kmode.data() : zero, 4 * kmode.size() + 4),
-                 o_scs = a.add(keep ? (const void*)kept.slots.data() : zero, 4 * kept.slots.size() + 4);
-    // (one section for everything the ring adds: a single verification still fits stage_h2d's arguments)
-    const size_t o_ring = use_ring ? a.add(rsec.data(), rsec.size()) : 0;
-    const size_t o_fill = n_fill ? a.add(a_fill.data(), 8 * n_fill) : 0;
-    const size_t o_dlist = n_dn ? a.add(ads.dense.data(), 4 * n_dn) : 0,
-                 o_rlist = n_dn && n_rest ? a.add(ads.rest.data(), 4 * n_rest) : 0,
-                 o_idx0 = n_dn ? a.add(pk_idx, 4 * n_idx) : 0, o_ktab = n_dn ? a.add(ktab.data(), 4 * n_keys) : 0;
-    // (pinned, behind the arena: the batch verdict word, the wave batch check's group verdicts, the
-    // dense key sums' per-item modes)
-    const size_t h_dmode = al256(al256(a.total) + 64 + 4 * wb_ng);
-    if ((rc = L.stage.ensure(h_dmode + 4 * n_dn)) || (rc = L.in.ensure(a.total))) return rc;
-    uint8_t* h = static_cast<uint8_t*>(L.stage.p);
-    for (size_t k = 0; k < a.parts.size(); k++)
-        if (a.parts[k].second) std::memcpy(h + a.offs[k], a.parts[k].first, a.parts[k].second);
-    // scratch: the call's key records + statuses, item sig / H / apk records, three status arrays,
-    // the batch check's shares (W-order Fp12 + Jacobian G1 per item) and its verdict word
-    const size_t w_krec = 0, w_kst = w_krec + 4 * G2_REC_WORDS * n_dec, w_srec = al256(w_kst + 4 * n_dec + 4),
-                 w_hrec = w_srec + 4 * G1_REC_WORDS * n, w_arec = w_hrec + 4 * G1_REC_WORDS * n,
-                 w_st = w_arec + 4 * G2_REC_WORDS * (n + 1), w_ssig = al256(w_st + 4 * n), w_sapk = al256(w_ssig + 4 * n),
-                 w_ok = al256(w_sapk + 4 * n), w_frec = al256(w_ok + 4),
-                 w_jrec = al256(w_frec + 4 * F12_REC_WORDS * (batch ? n + 1 : 0)),
-                 w_prec = al256(w_jrec + 4 * G1J_REC_WORDS * (batch ? n : 0)),
-                 w_hh = al256(w_prec + 4 * G1J_REC_WORDS * (batch ? n + 1 : 0) + 4),
-                 w_sdec = al256(w_hh + 4 * G1H_REC_WORDS * (wavem ? n : 0)), w_ssub = al256(w_sdec + 4 * n),
-                 w_spair = al256(w_ssub + 4 * n), w_aj = al256(w_spair + 4 * n + 4),
-                 w_wb = al256(w_aj + 4 * G2J_WORDS * (wavem ? n + wb_ng : 0) + 4),
-                 // the wave batch check's scratch: F records, [r] H, [r] sig, the groups' S_g, in-batch
-                 // flags, the groups' verdict words
-                 w_wf = w_wb, w_wp = al256(w_wf + 4 * FB_REC_WORDS * wb_m), w_wj = al256(w_wp + 4 * G1H_REC_WORDS * wb_m),
-                 w_wsg = al256(w_wj + 4 * G1J_REC_WORDS * (wbatch ? n : 0)),
-                 w_winb = al256(w_wsg + 4 * G1_REC_WORDS * wb_ng), w_wgok = al256(w_winb + 4 * (wbatch ? n : 0)),
-                 // the dense key sums' scratch: the key table's total and flag, the items' modes
-                 w_dtot = al256(w_wgok + 4 * wb_ng + 4), w_dmode = al256(w_dtot + 4 * (n_dn ? DT_WORDS : 0)),
-                 w_end = w_dmode + 4 * n_dn + 4;
-    if ((rc = L.work.ensure(w_end))) return rc;
-    uint8_t* in = static_cast<uint8_t*>(L.in.p);
-    uint8_t* w = static_cast<uint8_t*>(L.work.p);
-    KeyTab kt{cached ? static_cast<const uint32_t*>(d.kc.rec.p) : nullptr,
-              cached ? static_cast<const int32_t*>(d.kc.st.p) : nullptr, reinterpret_cast<uint32_t*>(w + w_krec),
-              reinterpret_cast<int32_t*>(w + w_kst),
-              cached && d.kc.lines_slots ? static_cast<const uint32_t*>(d.kc.lines.p) : nullptr,
-              cached ? static_cast<const uint32_t*>(d.kc.hrec.p) : nullptr,
-              use_apk ? static_cast<const uint32_t*>(d.ar.rec.p) : nullptr,
-              use_apk ? static_cast<const uint32_t*>(d.ar.lines.p) : nullptr};
-    const uint32_t* km = kside ? reinterpret_cast<const uint32_t*>(in + o_kmode) : nullptr;
-    auto* srec = reinterpret_cast<uint32_t*>(w + w_srec);
-    auto* hrec = reinterpret_cast<uint32_t*>(w + w_hrec);
-    auto* arec = reinterpret_cast<uint32_t*>(w + w_arec);
-    auto* st = reinterpret_cast<int32_t*>(w + w_st);
-    auto* ssig = reinterpret_cast<int32_t*>(w + w_ssig);
-    auto* sapk = reinterpret_cast<int32_t*>(w + w_sapk);
-    auto* okw = reinterpret_cast<int32_t*>(w + w_ok);
-    auto* frec = reinterpret_cast<uint32_t*>(w + w_frec);
-    auto* jrec = reinterpret_cast<uint32_t*>(w + w_jrec);
-    auto* prec = reinterpret_cast<uint32_t*>(w + w_prec);
-    auto* hh = reinterpret_cast<uint32_t*>(w + w_hh);
-    auto* sdec = reinterpret_cast<int32_t*>(w + w_sdec);
-    auto* ssub = reinterpret_cast<int32_t*>(w + w_ssub);
-    auto* spair = reinterpret_cast<int32_t*>(w + w_spair);
-    auto* ajrec = reinterpret_cast<uint32_t*>(w + w_aj);
-    hipStream_t s0 = L.stream, s1 = L.side[0], s2 = L.side[1];
-    kept.stream = s0;
+    const bool a_hit = !P.a_idx.empty();
+    P.k_off = a_hit ? P.a_off.data() : c.pk_off;
+    P.k_cnt = a_hit ? P.a_cnt.data() : c.pk_cnt;
+    P.k_idx = a_hit ? &P.a_idx : &P.remap;
     // the per-stage timing events of a small call only on a NWV_FLAG_BLS_STAGE_TIMES context: else
     // just the two that order the streams (the others cost a single verification ~0.1 ms:
     // 2.85 -> 2.72-2.81 ms, profiles/round6_bls_stage_timing_ab.json)
-    const bool no_timing = !(d.flags & NWV_FLAG_BLS_STAGE_TIMES);
-    bool untimed = false;  // a small call that recorded no stage events (set on that path only)
-    auto trec = [&](int k, hipStream_t s) { return no_timing ? hipSuccess : hipEventRecord(L.ev[k], s); };
-    // stage times of the completed call, its path and key counts -> the device's "last call"
-    uint64_t wb_stat[3] = {0, 0, 0}, kb_stat[5] = {0, 0, 0, 0, 0}, ad_stat[4] = {0, 0, 0, 0};
-    auto finish = [&](int path_done) -> int {
-        const int pairs[5][2] = {{0, 1}, {3, 4}, {5, 6}, {1, 2}, {7, 8}};  // keys, sigs, h2c, apk, pairing
-        double ms5[5] = {0, 0, 0, 0, 0};
-        for (int k = 0; k < 5 && !untimed; k++) {
-            float ms = 0;
-            BLS_HIP(hipEventElapsedTime(&ms, L.ev[pairs[k][0]], L.ev[pairs[k][1]]));
-            ms5[k] = ms;
-        }
-        std::lock_guard<std::mutex> g(d.stat_mu);
-        std::memcpy(d.last_ms, ms5, sizeof ms5);
-        d.last_path = path_done;
-        d.last_keys[0] = hits;
-        d.last_keys[1] = n_dec;
-        std::memcpy(d.last_batch, wb_stat, sizeof wb_stat);
-        std::memcpy(d.last_kbatch, kb_stat, sizeof kb_stat);
-        std::memcpy(d.last_apkd, ad_stat, sizeof ad_stat);
-        return NWV_OK;
-    };
-    BLS_HIP(nwv_stage::stage_h2d(in, h, a.total, s0));  // small calls: through kernel arguments
-    BLS_HIP(hipEventRecord(L.sev[0], s0));
-    BLS_HIP(hipStreamWaitEvent(s1, L.sev[0], 0));
-    if (wave_small) {
-        untimed = no_timing;
-        // a call of up to wave_max items on two streams (8 concurrent calls then fit 16 hardware
-        // queues one to one): side 0 decodes the keys the cache does not hold, then hashes to G1
-        // and sums the keys in one launch (k_blsw_pre); main decodes the signatures, then runs
-        // the pairing checks and the signatures' G1 checks in one launch (k_blsw_pair_sub)
-        BLS_HIP(trec(0, s1));
-        if (n_dec)
-            hipLaunchKernelGGL(k_bls_keys_fill, dim3(kBlocks(n_dec)), dim3(BLS_LANES), 0, s1, (uint32_t)n_dec,
-                               in + o_keys, reinterpret_cast<const uint32_t*>(in + o_kslot),
-                               const_cast<uint32_t*>(kt.rs), const_cast<int32_t*>(kt.ss));
-        BLS_HIP(trec(1, s1));
-        BLS_HIP(trec(5, s1));
-        if (use_ring)
-            hipLaunchKernelGGL(k_blsw_pre_r, dim3((unsigned)(2 * n)), dim3(64), 0, s1, (uint32_t)n, in + o_msg,
-                               reinterpret_cast<const uint64_t*>(in + o_moff),
-                               reinterpret_cast<const uint32_t*>(in + o_mlen), in + o_dst, (uint32_t)dl, hh, kt,
-                               reinterpret_cast<const uint32_t*>(in + o_off),
-                               reinterpret_cast<const uint32_t*>(in + o_cnt),
-                               reinterpret_cast<const uint32_t*>(in + o_idx), km, ajrec, sapk,
-                               static_cast<uint32_t*>(d.mr.rec.p),
-                               reinterpret_cast<const uint32_t*>(in + o_ring + r_hsrc),
-                               reinterpret_cast<const uint32_t*>(in + o_ring + r_hpub));
-        else
-            hipLaunchKernelGGL(k_blsw_pre, dim3((unsigned)(2 * n)), dim3(64), 0, s1, (uint32_t)n, in + o_msg,
-                               reinterpret_cast<const uint64_t*>(in + o_moff),
-                               reinterpret_cast<const uint32_t*>(in + o_mlen), in + o_dst, (uint32_t)dl, hh, kt,
-                               reinterpret_cast<const uint32_t*>(in + o_off),
-                               reinterpret_cast<const uint32_t*>(in + o_cnt),
-                               reinterpret_cast<const uint32_t*>(in + o_idx), km, ajrec, sapk);
-        if (n_fill) BLS_HIP(hipEventRecord(L.sev[2], s1));
-        BLS_HIP(trec(2, s1));
-        BLS_HIP(trec(6, s1));
-        BLS_HIP(trec(3, s0));
-        hipLaunchKernelGGL(k_blsw_sigdec, dim3(kBlocks(n)), dim3(BLS_LANES), 0, s0, (uint32_t)n, in + o_sigs, srec,
-                           sdec);
-        BLS_HIP(trec(4, s0));
-        BLS_HIP(hipEventRecord(L.sev[1], s0));
-        // the ahead messages on the main stream, idle from here on: the pairing, on side 0, does
-        // not wait for them
-        if (n_ah)
-            hipLaunchKernelGGL(k_blsw_h2c_ahead, dim3((unsigned)n_ah), dim3(64), 0, s0, (uint32_t)n_ah,
-                               (const uint8_t*)(in + o_ring + r_amsg), reinterpret_cast<const uint64_t*>(in + o_ring),
-                               reinterpret_cast<const uint32_t*>(in + o_ring + r_alen), (const uint8_t*)(in + o_dst),
-                               (uint32_t)dl, static_cast<uint32_t*>(d.mr.rec.p),
-                               reinterpret_cast<const uint32_t*>(in + o_ring + r_aslot));
-        // the aggregate-key fills on the main stream too, behind the key sums: they run beside the
-        // pairing kernel, which reads the sums and never the slots being filled
-        if (n_fill) {
-            BLS_HIP(hipStreamWaitEvent(s0, L.sev[2], 0));
-            hipLaunchKernelGGL(k_blsw_apk_fill, dim3((unsigned)n_fill), dim3(64), 0, s0, (uint32_t)n_fill,
-                               reinterpret_cast<const uint32_t*>(in + o_fill),
-                               reinterpret_cast<const uint32_t*>(in + o_fill + 4 * n_fill), (const uint32_t*)ajrec,
-                               (const int32_t*)sapk, static_cast<uint32_t*>(d.ar.rec.p),
-                               static_cast<uint32_t*>(d.ar.lines.p));
-        }
-        kept.stream = s1;  // k_blsw_status writes the ring slots there
-        // the rest runs on side 0 behind the hash, which ends after the signatures' decode (one
-        // lane each, ~0.45 ms against ~0.57 ms): its wait on the decode is already met, so the
-        // cross-queue hand-off (~25 us in the single-verify trace) is off the critical path
-        BLS_HIP(hipStreamWaitEvent(s1, L.sev[1], 0));
-        BLS_HIP(trec(7, s1));
-        static const bool sub_flat = [] {
-            const char* e = std::getenv("NWV_BLS_SUB_FLAT");
-            return e && std::atoi(e) != 0;
-        }();
-        if (sub_flat && ensure_pair_script()) return NWV_ERR_HIP;
-        hipLaunchKernelGGL(sub_flat ? k_blsw_pair_sub_f : k_blsw_pair_sub, dim3((unsigned)(2 * n)), dim3(64), 0, s1,
-                           (uint32_t)n,
-                           (const uint32_t*)srec, (const int32_t*)sdec, (const uint32_t*)hh, 1, (const uint32_t*)ajrec,
-                           (const int32_t*)sapk, kt, reinterpret_cast<const uint32_t*>(in + o_off),
-                           reinterpret_cast<const uint32_t*>(in + o_cnt), reinterpret_cast<const uint32_t*>(in + o_idx),
-                           km, spair, ssub);
-        BLS_HIP(trec(8, s1));
-        // (the verified records into the ring slots this call reserved)
-        hipLaunchKernelGGL(k_blsw_status, dim3(kBlocks(n)), dim3(BLS_LANES), 0, s1, (uint32_t)n,
-                           (const int32_t*)sdec, (const int32_t*)ssub, (const int32_t*)sapk, (const int32_t*)spair, st,
-                           (const uint32_t*)srec, keep ? static_cast<uint32_t*>(d.sc.rec.p) : nullptr,
-                           reinterpret_cast<const uint32_t*>(in + o_scs));
-        BLS_HIP(hipGetLastError());
-        BLS_HIP(hipMemcpyAsync(status, st, 4 * n, hipMemcpyDeviceToHost, s1));
-        BLS_HIP(hipStreamSynchronize(s1));
-        if (n_ah || n_fill) BLS_HIP(hipStreamSynchronize(s0));
-        if (keep) {
-            d.sc.publish(n, sigs, status, kept.slots);
-            kept.sc = nullptr;
-        }
-        // H(m) is a function of dst and message alone: a miss is published whatever its item's
-        // status; an ahead message only behind its gate
-        ms.finish(status, mcount);
-        if (mstat)
-            for (int k = 0; k < 5; k++) mstat[k] += mcount[k];
-        // a set is a function of the key cache's slots alone, but it is kept only behind a verified
-        // aggregate: peers cannot churn the ring without valid certificates
-        as.finish(status, acount);
-        if (astat)
-            for (int k = 0; k < 4; k++) astat[k] += acount[k];
-        return finish(3);
+    P.no_timing = !(d.flags & NWV_FLAG_BLS_STAGE_TIMES);
+    return NWV_OK;
+}
+
+// the call's typed buffers: the arena's sections on the device (the host side is filled from the
+// arena's parts), the scratch sections, the pinned words behind the arena
+struct CallBufs {
+    size_t n = 0, dl = 0;
+    // arena (device side)
+    const uint8_t *keys, *sigs, *msg, *dst, *seed, *amsg;
+    const uint32_t *kslot, *off, *cnt, *idx, *mlen, *km, *scs, *hsrc, *hpub, *aslot, *alen, *fill_item, *fill_slot,
+        *dlist, *rlist, *idx0, *ktab;
+    const uint64_t *moff, *aoff;
+    // scratch: item sig / H / apk records, the status arrays, the group batch check's shares
+    // (W-order Fp12 + Jacobian G1 per item) and its verdict word, the wave engine's records
+    uint32_t *srec, *hrec, *arec, *frec, *jrec, *prec, *hh, *ajrec;
+    int32_t *st, *ssig, *sapk, *okw, *sdec, *ssub, *spair;
+    // the wave batch check's scratch: F records, [r] H, [r] sig, the groups' S_g, in-batch flags,
+    // the groups' verdict words
+    uint32_t *wf, *wp, *wj, *wsg, *winb;
+    int32_t* wgok;
+    // the dense key sums' scratch: the key table's total and flag, the items' modes
+    uint32_t *dtot, *dmode;
+    KeyTab kt;
+    // pinned, behind the arena: the batch verdict word, the wave batch check's group verdicts, the
+    // dense key sums' per-item modes
+    int32_t *h_ok, *h_gok;
+    uint32_t* h_dmode;
+};
+
+hipError_t trec(const CallPlan& P, BlsLane& L, int k, hipStream_t s) {
+    return P.no_timing ? hipSuccess : hipEventRecord(L.ev[k], s);
+}
+// the call's keys the cache does not hold, decoded into the scratch table
+void launch_keys_fill(hipStream_t s, const CallPlan& P, const CallBufs& B) {
+    if (P.n_dec())
+        hipLaunchKernelGGL(k_bls_keys_fill, dim3(kBlocks(P.n_dec())), dim3(BLS_LANES), 0, s, (uint32_t)P.n_dec(),
+                           B.keys, B.kslot, const_cast<uint32_t*>(B.kt.rs), const_cast<int32_t*>(B.kt.ss));
+}
+// the tail of every path: the statuses to the caller (with one more copy, when given), the stream
+// synchronised
+int copy_back(hipStream_t s, const CallBufs& B, int32_t* status, void* xdst = nullptr, const void* xsrc = nullptr,
+              size_t xbytes = 0) {
+    BLS_HIP(hipGetLastError());
+    BLS_HIP(hipMemcpyAsync(status, B.st, 4 * B.n, hipMemcpyDeviceToHost, s));
+    if (xbytes) BLS_HIP(hipMemcpyAsync(xdst, xsrc, xbytes, hipMemcpyDeviceToHost, s));
+    BLS_HIP(hipStreamSynchronize(s));
+    return NWV_OK;
+}
+// the wave paths' tail: the statuses in the oracle's order first (sc_rec: the verified records
+// into the ring slots this call reserved)
+int wave_status_back(hipStream_t s, const CallBufs& B, int32_t* status, void* sc_rec, void* xdst = nullptr,
+                     const void* xsrc = nullptr, size_t xbytes = 0) {
+    hipLaunchKernelGGL(k_blsw_status, dim3(kBlocks(B.n)), dim3(BLS_LANES), 0, s, (uint32_t)B.n, B.sdec, B.ssub,
+                       B.sapk, B.spair, B.st, B.srec, static_cast<uint32_t*>(sc_rec), sc_rec ? B.scs : nullptr);
+    return copy_back(s, B, status, xdst, xsrc, xbytes);
+}
+
+// The small wave call (path 3): a call of up to wave_max items on two streams (8 concurrent calls
+// then fit 16 hardware queues one to one): side 0 decodes the keys the cache does not hold, then
+// hashes to G1 and sums the keys in one launch (k_blsw_pre); main decodes the signatures, then runs
+// the pairing checks and the signatures' G1 checks in one launch (k_blsw_pair_sub)
+int run_small(BlsDev& d, BlsLane& L, CallPlan& P, const CallBufs& B, const CallIn& c, int32_t* status,
+              CallSlots& S, uint64_t* mstat, uint64_t* astat, CallStats& T) {
+    const size_t n = c.n;
+    const hipStream_t s0 = L.stream, s1 = L.side[0];
+    T.untimed = P.no_timing;
+    T.path = 3;
+    BLS_HIP(trec(P, L, 0, s1));
+    launch_keys_fill(s1, P, B);
+    BLS_HIP(trec(P, L, 1, s1));
+    BLS_HIP(trec(P, L, 5, s1));
+    if (P.use_ring)
+        hipLaunchKernelGGL(k_blsw_pre_r, dim3((unsigned)(2 * n)), dim3(64), 0, s1, (uint32_t)n, B.msg, B.moff, B.mlen,
+                           B.dst, (uint32_t)B.dl, B.hh, B.kt, B.off, B.cnt, B.idx, B.km, B.ajrec, B.sapk,
+                           static_cast<uint32_t*>(d.mr.rec.p), B.hsrc, B.hpub);
+    else
+        hipLaunchKernelGGL(k_blsw_pre, dim3((unsigned)(2 * n)), dim3(64), 0, s1, (uint32_t)n, B.msg, B.moff, B.mlen,
+                           B.dst, (uint32_t)B.dl, B.hh, B.kt, B.off, B.cnt, B.idx, B.km, B.ajrec, B.sapk);
+    if (P.n_fill) BLS_HIP(hipEventRecord(L.sev[2], s1));
+    BLS_HIP(trec(P, L, 2, s1));
+    BLS_HIP(trec(P, L, 6, s1));
+    BLS_HIP(trec(P, L, 3, s0));
+    hipLaunchKernelGGL(k_blsw_sigdec, dim3(kBlocks(n)), dim3(BLS_LANES), 0, s0, (uint32_t)n, B.sigs, B.srec, B.sdec);
+    BLS_HIP(trec(P, L, 4, s0));
+    BLS_HIP(hipEventRecord(L.sev[1], s0));
+    // the ahead messages on the main stream, idle from here on: the pairing, on side 0, does
+    // not wait for them
+    if (P.n_ah) launch_ahead(s0, P.n_ah, B.amsg, B.aoff, B.alen, B.dst, B.dl, d.mr.rec.p, B.aslot);
+    // the aggregate-key fills on the main stream too, behind the key sums: they run beside the
+    // pairing kernel, which reads the sums and never the slots being filled
+    if (P.n_fill) {
+        BLS_HIP(hipStreamWaitEvent(s0, L.sev[2], 0));
+        hipLaunchKernelGGL(k_blsw_apk_fill, dim3((unsigned)P.n_fill), dim3(64), 0, s0, (uint32_t)P.n_fill, B.fill_item,
+                           B.fill_slot, B.ajrec, B.sapk, static_cast<uint32_t*>(d.ar.rec.p),
+                           static_cast<uint32_t*>(d.ar.lines.p));
     }
+    S.kept.stream = s1;  // k_blsw_status writes the ring slots there
+    // the rest runs on side 0 behind the hash, which ends after the signatures' decode (one
+    // lane each, ~0.45 ms against ~0.57 ms): its wait on the decode is already met, so the
+    // cross-queue hand-off (~25 us in the single-verify trace) is off the critical path
+    BLS_HIP(hipStreamWaitEvent(s1, L.sev[1], 0));
+    BLS_HIP(trec(P, L, 7, s1));
+    hipLaunchKernelGGL(k_blsw_pair_sub, dim3((unsigned)(2 * n)), dim3(64), 0, s1, (uint32_t)n, B.srec, B.sdec, B.hh, 1,
+                       B.ajrec, B.sapk, B.kt, B.off, B.cnt, B.idx, B.km, B.spair, B.ssub);
+    BLS_HIP(trec(P, L, 8, s1));
+    int rc = wave_status_back(s1, B, status, P.keep ? d.sc.rec.p : nullptr);
+    if (rc) return rc;
+    if (P.n_ah || P.n_fill) BLS_HIP(hipStreamSynchronize(s0));
+    if (P.keep) {
+        d.sc.publish(n, c.sigs, status, S.kept.slots);
+        S.kept.sc = nullptr;
+    }
+    // H(m) is a function of dst and message alone: a miss is published whatever its item's
+    // status; an ahead message only behind its gate
+    S.ms.finish(status, P.mcount);
+    if (mstat)
+        for (int k = 0; k < 5; k++) mstat[k] += P.mcount[k];
+    // a set is a function of the key cache's slots alone, but it is kept only behind a verified
+    // aggregate: peers cannot churn the ring without valid certificates
+    S.as.finish(status, P.acount);
+    if (astat)
+        for (int k = 0; k < 4; k++) astat[k] += P.acount[k];
+    return NWV_OK;
+}
+
+// the large calls' prologue: side 0 decodes the keys the cache does not hold and sums every item's
+// keys, side 1 hashes every item's message to G1 (the statuses are not known yet); ev[10] and
+// ev[11] mark their ends
+int large_sides(BlsLane& L, const CallPlan& P, const CallBufs& B, const CallIn& c) {
+    const size_t n = c.n, n_dn = P.ads.dense.size(), n_rest = P.ads.rest.size();
     if (!L.side[1] && nwv::lane_stream_create(&L.side[1], L.high) != hipSuccess)
         return nwv_internal_set_err(NWV_ERR_HIP, "bls stream");
-    s2 = L.side[1];
+    const hipStream_t s1 = L.side[0], s2 = L.side[1];
     BLS_HIP(hipStreamWaitEvent(s2, L.sev[0], 0));
-    // side 0: keys, key sums
     BLS_HIP(hipEventRecord(L.ev[0], s1));
-    if (n_dec)
-        hipLaunchKernelGGL(k_bls_keys_fill, dim3(kBlocks(n_dec)), dim3(BLS_LANES), 0, s1, (uint32_t)n_dec, in + o_keys,
-                           reinterpret_cast<const uint32_t*>(in + o_kslot), const_cast<uint32_t*>(kt.rs),
-                           const_cast<int32_t*>(kt.ss));
+    launch_keys_fill(s1, P, B);
     BLS_HIP(hipEventRecord(L.ev[1], s1));
-    auto* dtot = reinterpret_cast<uint32_t*>(w + w_dtot);
-    auto* dmode = reinterpret_cast<uint32_t*>(w + w_dmode);
-    if (wavem && n_dn) {
+    if (P.wavem && n_dn) {
         // the dense stage: the key table's total, the dense items L lanes each, then the items
         // left to the per-item code through their list (all three write disjoint records)
-        const DenseKeys dk{kt.hrc, kt.sc, reinterpret_cast<const uint32_t*>(in + o_ktab), (uint32_t)n_keys, KC_CAP};
-        const auto* d_list = reinterpret_cast<const uint32_t*>(in + o_dlist);
-        const auto* p_off = reinterpret_cast<const uint32_t*>(in + o_off);
-        const auto* p_cnt = reinterpret_cast<const uint32_t*>(in + o_cnt);
-        const auto* p_idx0 = reinterpret_cast<const uint32_t*>(in + o_idx0);
-        hipLaunchKernelGGL(k_blsd_total, dim3(1), dim3(64), 0, s1, dk, dtot);
-        const unsigned per = 64 / ad_lanes, blocks = (unsigned)((n_dn + per - 1) / per);
-        auto* kern = ad_lanes == 16 ? k_blsd_apk<16> : ad_lanes == 8 ? k_blsd_apk<8> : k_blsd_apk<4>;
-        hipLaunchKernelGGL(kern, dim3(blocks), dim3(64), 0, s1, (uint32_t)n_dn, d_list, dk, p_off, p_cnt, p_idx0,
-                           (const uint32_t*)dtot, ajrec, sapk, dmode);
+        const DenseKeys dk{B.kt.hrc, B.kt.sc, B.ktab, (uint32_t)c.n_keys, KC_CAP};
+        hipLaunchKernelGGL(k_blsd_total, dim3(1), dim3(64), 0, s1, dk, B.dtot);
+        const unsigned per = 64 / P.ad_lanes, blocks = (unsigned)((n_dn + per - 1) / per);
+        auto* kern = P.ad_lanes == 16 ? k_blsd_apk<16> : P.ad_lanes == 8 ? k_blsd_apk<8> : k_blsd_apk<4>;
+        hipLaunchKernelGGL(kern, dim3(blocks), dim3(64), 0, s1, (uint32_t)n_dn, B.dlist, dk, B.off, B.cnt, B.idx0,
+                           B.dtot, B.ajrec, B.sapk, B.dmode);
         if (n_rest)
-            hipLaunchKernelGGL(k_blsw_apk_list, dim3((unsigned)n_rest), dim3(64), 0, s1, (uint32_t)n_rest,
-                               reinterpret_cast<const uint32_t*>(in + o_rlist), kt, p_off, p_cnt,
-                               reinterpret_cast<const uint32_t*>(in + o_idx), km, ajrec, sapk);
-    } else if (wavem)
-        hipLaunchKernelGGL(k_blsw_apk, dim3((unsigned)n), dim3(64), 0, s1, (uint32_t)n, kt,
-                           reinterpret_cast<const uint32_t*>(in + o_off), reinterpret_cast<const uint32_t*>(in + o_cnt),
-                           reinterpret_cast<const uint32_t*>(in + o_idx), km, ajrec, sapk);
+            hipLaunchKernelGGL(k_blsw_apk_list, dim3((unsigned)n_rest), dim3(64), 0, s1, (uint32_t)n_rest, B.rlist,
+                               B.kt, B.off, B.cnt, B.idx, B.km, B.ajrec, B.sapk);
+    } else if (P.wavem)
+        hipLaunchKernelGGL(k_blsw_apk, dim3((unsigned)n), dim3(64), 0, s1, (uint32_t)n, B.kt, B.off, B.cnt, B.idx, B.km,
+                           B.ajrec, B.sapk);
     else
-        hipLaunchKernelGGL(k_bls_apk_g, dim3(gBlocks(n)), dim3(BLS_LANES), 0, s1, (uint32_t)n, kt,
-                           reinterpret_cast<const uint32_t*>(in + o_off), reinterpret_cast<const uint32_t*>(in + o_cnt),
-                           reinterpret_cast<const uint32_t*>(in + o_idx), arec, sapk);
+        hipLaunchKernelGGL(k_bls_apk_g, dim3(gBlocks(n)), dim3(BLS_LANES), 0, s1, (uint32_t)n, B.kt, B.off, B.cnt, B.idx,
+                           B.arec, B.sapk);
     BLS_HIP(hipEventRecord(L.ev[2], s1));
     BLS_HIP(hipEventRecord(L.ev[10], s1));
-    // side 1: hash to G1 (every item: the statuses are not known yet)
     BLS_HIP(hipEventRecord(L.ev[5], s2));
-    // hash to G1: lane pairs (NWV_BLS_H2C_GROUP=1: the 8-lane group form)
-    static const bool h2c_group = [] {
-        const char* e = std::getenv("NWV_BLS_H2C_GROUP");
-        return e && std::atoi(e) != 0;
-    }();
-    if (!h2c_group)
-        hipLaunchKernelGGL(k_bls_h2c_2, dim3((unsigned)((n + BLS_LANES / 2 - 1) / (BLS_LANES / 2))), dim3(BLS_LANES), 0,
-                           s2, (uint32_t)n, in + o_msg, reinterpret_cast<const uint64_t*>(in + o_moff),
-                           reinterpret_cast<const uint32_t*>(in + o_mlen), in + o_dst, (uint32_t)dl, hrec, km);
-    else
-    hipLaunchKernelGGL(k_bls_h2c_g, dim3(gBlocks(n)), dim3(BLS_LANES), 0, s2, (uint32_t)n, in + o_msg,
-                       reinterpret_cast<const uint64_t*>(in + o_moff), reinterpret_cast<const uint32_t*>(in + o_mlen),
-                       in + o_dst, (uint32_t)dl, hrec, km);
+    // hash to G1 on lane pairs
+    hipLaunchKernelGGL(k_bls_h2c_2, dim3((unsigned)((n + BLS_LANES / 2 - 1) / (BLS_LANES / 2))), dim3(BLS_LANES), 0, s2,
+                       (uint32_t)n, B.msg, B.moff, B.mlen, B.dst, (uint32_t)B.dl, B.hrec, B.km);
     BLS_HIP(hipEventRecord(L.ev[6], s2));
     BLS_HIP(hipEventRecord(L.ev[11], s2));
-    if (wavem) {
-        // large wave calls: the one-lane-per-item decode + G1 check of the group path, which keeps
-        // every lane busy (an all-Ok subgroup column), then every item's pairing check on a wave
-        BLS_HIP(hipEventRecord(L.ev[3], s0));
-        hipLaunchKernelGGL(k_bls_sigs, dim3(kBlocks(n)), dim3(BLS_LANES), 0, s0, (uint32_t)n, in + o_sigs, srec, sdec);
-        BLS_HIP(hipMemsetAsync(ssub, 0, 4 * n, s0));
-        BLS_HIP(hipEventRecord(L.ev[4], s0));
-        BLS_HIP(hipStreamWaitEvent(s0, L.ev[10], 0));
-        BLS_HIP(hipStreamWaitEvent(s0, L.ev[11], 0));
-        BLS_HIP(hipEventRecord(L.ev[7], s0));
-        // items per pairing wave (env NWV_BLS_PACK, 1..4): one LDS bank of ~6.5 KB each
-        static const uint32_t pack = [] {
-            const char* e = std::getenv("NWV_BLS_PACK");
-            const long v = e ? std::strtol(e, nullptr, 10) : 3;
-            return (uint32_t)(v < 1 ? 1 : v > BLS_PACK_MAX ? BLS_PACK_MAX : v);
-        }();
-        // diagnostic (occupancy experiments): NWV_BLS_LDS_PAD bytes of extra LDS per pairing wave
-        static const size_t lds_pad = [] {
-            const char* e = std::getenv("NWV_BLS_LDS_PAD");
-            return e ? (size_t)std::strtoull(e, nullptr, 10) : (size_t)0;
-        }();
-        // (every item's keys cached is what the key side already asks: kside)
-        const bool kb_cand = !wave_small && kside && kb_min > 0 && n >= kb_min;
-        if ((pack > 1 || wbatch || kb_cand) && ensure_pair_script()) return NWV_ERR_HIP;
-        const auto* d_off = reinterpret_cast<const uint32_t*>(in + o_off);
-        const auto* d_cnt = reinterpret_cast<const uint32_t*>(in + o_cnt);
-        const auto* d_idx = reinterpret_cast<const uint32_t*>(in + o_idx);
-        // the per-item pairing checks of items [lo, lo + m): every item's own final exponentiation
-        auto per_item_range = [&](size_t lo, size_t m) {
-            if (pack > 1)
-                hipLaunchKernelGGL(k_blsw_pair_k, dim3((unsigned)((m + pack - 1) / pack)), dim3(64),
-                                   (size_t)4 * (wave::KP_WORDS + pack * wave::SW * wave::NSLOTS_PC) + lds_pad, s0,
-                                   (uint32_t)m, pack, (const uint32_t*)srec + G1_REC_WORDS * lo,
-                                   (const int32_t*)sdec + lo, (const uint32_t*)hrec + G1_REC_WORDS * lo, 0,
-                                   (const uint32_t*)ajrec + G2J_WORDS * lo, (const int32_t*)sapk + lo, kt, d_off + lo,
-                                   d_cnt + lo, d_idx, km ? km + lo : nullptr, spair + lo);
-            else
-                hipLaunchKernelGGL(k_blsw_pair, dim3((unsigned)m), dim3(64), lds_pad, s0, (uint32_t)m,
-                                   (const uint32_t*)srec + G1_REC_WORDS * lo, (const int32_t*)sdec + lo,
-                                   (const uint32_t*)hrec + G1_REC_WORDS * lo, 0, (const uint32_t*)ajrec + G2J_WORDS * lo,
-                                   (const int32_t*)sapk + lo, kt, d_off + lo, d_cnt + lo, d_idx,
-                                   km ? km + lo : nullptr, spair + lo);
-        };
-        int path_done = 3;
-        bool kb_done = false;
-        if (kb_cand) {
-            // the pre-pairing statuses come back first: the plan groups the items they leave
-            if ((rc = L.kb_st.ensure(12 * n + 64))) return rc;
-            int32_t* h_dec = static_cast<int32_t*>(L.kb_st.p);
-            int32_t *h_apk = h_dec + n, *h_gok = h_apk + n;
-            BLS_HIP(hipMemcpyAsync(h_dec, sdec, 4 * n, hipMemcpyDeviceToHost, s0));
-            BLS_HIP(hipMemcpyAsync(h_apk, sapk, 4 * n, hipMemcpyDeviceToHost, s0));
-            BLS_HIP(hipStreamSynchronize(s0));
-            std::vector<uint8_t> ok(n), el(n);
-            for (size_t i = 0; i < n; i++) {
-                ok[i] = h_dec[i] == ST_OK && h_apk[i] == ST_OK;
-                // (a compressed identity has bit 6 of its first byte set; the kernels check again)
-                el[i] = ok[i] && kmode[i] && !(sigs[48 * i] & 0x40);
-            }
-            nwv::KeyBatchPlan P;
-            nwv::key_batch_plan(n, ok.data(), el.data(), pk_off, pk_cnt, remap.data(), d.kc.used, kb_grp, kb_ratio, P);
-            if (P.run) {
-                const size_t ne = P.items.size(), ng = P.groups(), M = P.entries(), C = P.cidx.size(), KM = M + ng;
-                // the plan's lists, one copy: items | goff | eslot | egrp | coff | cidx | 0..M-1 | ones
-                const size_t u_goff = ne, u_eslot = u_goff + ng + 1, u_egrp = u_eslot + M, u_coff = u_egrp + M,
-                             u_cidx = u_coff + M + 1, u_iota = u_cidx + C, u_ones = u_iota + M, u_end = u_ones + M;
-                if ((rc = L.kb_up.ensure(4 * u_end)) || (rc = L.kb_in.ensure(4 * u_end))) return rc;
-                uint32_t* up = static_cast<uint32_t*>(L.kb_up.p);
-                std::memcpy(up, P.items.data(), 4 * ne);
-                std::memcpy(up + u_goff, P.goff.data(), 4 * (ng + 1));
-                std::memcpy(up + u_eslot, P.eslot.data(), 4 * M);
-                std::memcpy(up + u_egrp, P.egrp.data(), 4 * M);
-                std::memcpy(up + u_coff, P.coff.data(), 4 * (M + 1));
-                std::memcpy(up + u_cidx, P.cidx.data(), 4 * C);
-                for (size_t m = 0; m < M; m++) {
-                    up[u_iota + m] = (uint32_t)m;
-                    up[u_ones + m] = 1u;
-                }
-                const uint32_t* ki = static_cast<const uint32_t*>(L.kb_in.p);
-                BLS_HIP(hipMemcpyAsync(L.kb_in.p, up, 4 * u_end, hipMemcpyHostToDevice, s0));
-                // the check's records: [r] H and [r] sig per position, S_g per group, the Miller
-                // entries' hash sides, Qs and F records, the groups' poison and verdict words
-                const size_t k_sj = al256(4 * G1J_REC_WORDS * ne), k_sg = al256(k_sj + 4 * G1J_REC_WORDS * ne),
-                             k_p = al256(k_sg + 4 * G1_REC_WORDS * ng), k_q = al256(k_p + 4 * G1H_REC_WORDS * KM),
-                             k_f = al256(k_q + 4 * G2J_WORDS * KM), k_poi = al256(k_f + 4 * FB_REC_WORDS * KM),
-                             k_gok = k_poi + 4 * ng, k_end = k_gok + 4 * ng + 4;
-                if ((rc = L.kb_work.ensure(k_end))) return rc;
-                uint8_t* kw = static_cast<uint8_t*>(L.kb_work.p);
-                auto* khj = reinterpret_cast<uint32_t*>(kw);
-                auto* ksj = reinterpret_cast<uint32_t*>(kw + k_sj);
-                auto* ksg = reinterpret_cast<uint32_t*>(kw + k_sg);
-                auto* kp = reinterpret_cast<uint32_t*>(kw + k_p);
-                auto* kq = reinterpret_cast<uint32_t*>(kw + k_q);
-                auto* kf = reinterpret_cast<uint32_t*>(kw + k_f);
-                auto* kpoi = reinterpret_cast<uint32_t*>(kw + k_poi);
-                auto* kgok = reinterpret_cast<int32_t*>(kw + k_gok);
-                const uint32_t G = kb_grp, gmax = (uint32_t)std::min<size_t>(G, ne);
-                uint32_t kmax = 0;
-                for (size_t g = 0; g < ng; g++) kmax = std::max(kmax, P.goff[g + 1] - P.goff[g]);
-                BLS_HIP(hipMemsetAsync(kpoi, 0, 8 * ng, s0));  // no poison; a group whose tree does not finish stays rejected
-                hipLaunchKernelGGL(k_blsk_rlc_pts, dim3(kBlocks(2 * ne)), dim3(BLS_LANES), 0, s0, (uint32_t)ne, G, ki,
-                                   (const uint32_t*)srec, (const uint32_t*)hrec, (const int32_t*)sdec,
-                                   (const int32_t*)sapk, (const uint8_t*)(in + o_seed), khj, ksj, kpoi);
-                for (uint32_t m = gmax; m > 1; m = (m + 1) / 2)
-                    hipLaunchKernelGGL(k_blsw_sfold, dim3(kBlocks(ng * ((m + 1) / 2))), dim3(BLS_LANES), 0, s0,
-                                       (uint32_t)ne, G, (uint32_t)ng, m, ksj);
-                hipLaunchKernelGGL(k_blsk_key_sums, dim3((unsigned)M), dim3(64), 0, s0, (uint32_t)M, ki + u_coff,
-                                   ki + u_cidx, ki + u_eslot, ki + u_egrp, (const uint32_t*)khj, kt, kp, kq, kpoi);
-                hipLaunchKernelGGL(k_blsk_sig_items, dim3(kBlocks(ng)), dim3(BLS_LANES), 0, s0, (uint32_t)ng, G,
-                                   (uint32_t)M, (const uint32_t*)ksj, ksg, kp, kq);
-                // every key entry as a one-key key-side item of its own: key list entry m = slot eslot[m]
-                const MillArgs ma{(uint32_t)M, ksg, ki + u_ones, kf};
-                hipLaunchKernelGGL(k_blsw_mill_k, dim3((unsigned)((KM + pack - 1) / pack)), dim3(64),
-                                   (size_t)4 * (wave::KP_WORDS + pack * wave::SW * wave::NSLOTS_PC) + lds_pad, s0,
-                                   (uint32_t)KM, pack, ma, (const uint32_t*)kp, (const uint32_t*)kq, kt, ki + u_iota,
-                                   ki + u_ones, ki + u_eslot, ki + u_ones);
-                for (uint32_t s = 1;; s *= WB_FAN) {
-                    const uint32_t ents = (kmax + 1 + s - 1) / s, wpg = (ents + WB_FAN - 1) / WB_FAN;
-                    hipLaunchKernelGGL(k_blsk_ffold, dim3((unsigned)(ng * wpg)), dim3(64), 0, s0, (uint32_t)ng,
-                                       ki + u_goff, (uint32_t)M, wpg, s, wpg == 1 ? 1 : 0, kf, (const uint32_t*)kpoi, kgok);
-                    if (wpg == 1) break;
-                }
-                hipLaunchKernelGGL(k_blsk_mark, dim3(kBlocks(ne)), dim3(BLS_LANES), 0, s0, (uint32_t)ne, G, ki,
-                                   (const int32_t*)kgok, spair);
-                BLS_HIP(hipGetLastError());
-                BLS_HIP(hipMemcpyAsync(h_gok, kgok, 4 * ng, hipMemcpyDeviceToHost, s0));
-                BLS_HIP(hipStreamSynchronize(s0));
-                // per item: the OK items outside the groups and every rejected group's items, in
-                // shared launches as the wave batch check shares them
-                std::vector<uint8_t> need(n, 0), ing(n, 0);
-                for (uint32_t i : P.outside) need[i] = 1;
-                for (uint32_t i : P.items) ing[i] = 1;
-                for (size_t g = 0; g < ng; g++) {
-                    if (h_gok[g] == 1) continue;
-                    kb_stat[1]++;
-                    for (uint32_t p = P.gfirst[g]; p < P.gfirst[g + 1]; p++) need[P.items[p]] = 1;
-                }
-                for (const auto& r : nwv::key_batch_ranges(n, need.data(), 1024)) {
-                    per_item_range(r.first, r.second - r.first);
-                    for (size_t i = r.first; i < r.second; i++) kb_stat[2] += ing[i];
-                }
-                kb_stat[0] = ng;
-                kb_stat[3] = KM;
-                kb_stat[4] = ne;
-                path_done = kb_stat[1] ? 7 : 6;
-                kb_done = true;
-            }
-        }
-        if (!kb_done && wbatch) {
-            auto* wf = reinterpret_cast<uint32_t*>(w + w_wf);
-            auto* wp = reinterpret_cast<uint32_t*>(w + w_wp);
-            auto* wj = reinterpret_cast<uint32_t*>(w + w_wj);
-            auto* wsg = reinterpret_cast<uint32_t*>(w + w_wsg);
-            auto* winb = reinterpret_cast<uint32_t*>(w + w_winb);
-            auto* wgok = reinterpret_cast<int32_t*>(w + w_wgok);
-            const uint32_t G = (uint32_t)wb_grp, ng = (uint32_t)wb_ng, gmax = (uint32_t)std::min<size_t>(wb_grp, n);
-            BLS_HIP(hipMemsetAsync(wgok, 0, 4 * wb_ng, s0));  // a group whose tree does not finish stays rejected
-            hipLaunchKernelGGL(k_blsw_rlc_pts, dim3(kBlocks(2 * n)), dim3(BLS_LANES), 0, s0, (uint32_t)n,
-                               (const uint32_t*)srec, (const uint32_t*)hrec, (const int32_t*)sdec, (const int32_t*)sapk, km,
-                               (const uint8_t*)(in + o_seed), wp, wj, winb, spair);
-            for (uint32_t m = gmax; m > 1; m = (m + 1) / 2)
-                hipLaunchKernelGGL(k_blsw_sfold, dim3(kBlocks((size_t)ng * ((m + 1) / 2))), dim3(BLS_LANES), 0, s0,
-                                   (uint32_t)n, G, ng, m, wj);
-            hipLaunchKernelGGL(k_blsw_sig_items, dim3(kBlocks(ng)), dim3(BLS_LANES), 0, s0, (uint32_t)n, G, ng,
-                               (const uint32_t*)wj, wsg, wp, ajrec);
-            const MillArgs ma{(uint32_t)n, wsg, winb, wf};
-            hipLaunchKernelGGL(k_blsw_mill_k, dim3((unsigned)((wb_m + pack - 1) / pack)), dim3(64),
-                               (size_t)4 * (wave::KP_WORDS + pack * wave::SW * wave::NSLOTS_PC) + lds_pad, s0,
-                               (uint32_t)wb_m, pack, ma, (const uint32_t*)wp, (const uint32_t*)ajrec, kt, d_off, d_cnt,
-                               d_idx, km);
-            for (uint32_t s = 1;; s *= WB_FAN) {
-                const uint32_t ents = (gmax + 1 + s - 1) / s, wpg = (ents + WB_FAN - 1) / WB_FAN;
-                hipLaunchKernelGGL(k_blsw_ffold, dim3(ng * wpg), dim3(64), 0, s0, (uint32_t)n, G, wpg, s,
-                                   wpg == 1 ? 1 : 0, wf, wgok);
-                if (wpg == 1) break;
-            }
-            hipLaunchKernelGGL(k_blsw_mark, dim3(kBlocks(n)), dim3(BLS_LANES), 0, s0, (uint32_t)n, G,
-                               (const int32_t*)wgok, (const uint32_t*)winb, spair);
-            BLS_HIP(hipGetLastError());
-            int32_t* hgok = reinterpret_cast<int32_t*>(h + al256(a.total) + 64);  // pinned: the groups' verdicts
-            BLS_HIP(hipMemcpyAsync(hgok, wgok, 4 * wb_ng, hipMemcpyDeviceToHost, s0));
-            BLS_HIP(hipStreamSynchronize(s0));
-            // every rejected group's items per item.  A launch over a few items costs one item's
-            // whole chain (~3 ms) however few they are, so rejected groups less than WB_GAP items
-            // apart share a launch with the accepted groups between them (~1 us an item there)
-            constexpr size_t WB_GAP = 1024;
-            wb_stat[0] = wb_ng;
-            for (size_t g = 0; g < wb_ng;) {
-                if (hgok[g] == 1) {
-                    g++;
-                    continue;
-                }
-                size_t e = g + 1;  // the range's end: past its last rejected group
-                wb_stat[1]++;
-                for (size_t q = e; q < wb_ng && (q - e) * wb_grp < WB_GAP; q++)
-                    if (hgok[q] != 1) {
-                        e = q + 1;
-                        wb_stat[1]++;
-                    }
-                const size_t lo = g * wb_grp, hi = std::min(n, e * wb_grp);
-                per_item_range(lo, hi - lo);
-                wb_stat[2] += hi - lo;
-                g = e;
-            }
-            path_done = wb_stat[1] ? 5 : 4;
-        } else if (!kb_done) {
-            per_item_range(0, n);
-        }
-        BLS_HIP(hipEventRecord(L.ev[8], s0));
-        hipLaunchKernelGGL(k_blsw_status, dim3(kBlocks(n)), dim3(BLS_LANES), 0, s0, (uint32_t)n,
-                           (const int32_t*)sdec, (const int32_t*)ssub, (const int32_t*)sapk, (const int32_t*)spair, st,
-                           (const uint32_t*)srec, nullptr, nullptr);
-        BLS_HIP(hipGetLastError());
-        BLS_HIP(hipMemcpyAsync(status, st, 4 * n, hipMemcpyDeviceToHost, s0));
-        const uint32_t* h_dm = reinterpret_cast<const uint32_t*>(h + h_dmode);
-        if (n_dn) BLS_HIP(hipMemcpyAsync(h + h_dmode, dmode, 4 * n_dn, hipMemcpyDeviceToHost, s0));
-        BLS_HIP(hipStreamSynchronize(s0));
-        if (ad_run) {
-            for (size_t q = 0; q < n_dn; q++) ad_stat[h_dm[q] ? 1 : 0]++;
-            ad_stat[2] = n_rest;
-            ad_stat[3] = ad_lanes;
-        }
-        return finish(path_done);
+    return NWV_OK;
+}
+
+// LDS bytes of a packed pairing wave (k_blsw_pair_k, k_blsw_mill_k)
+size_t pack_lds(const BlsEnv& env) {
+    return (size_t)4 * (wave::KP_WORDS + env.pack * wave::SW * wave::NSLOTS_PC) + env.lds_pad;
+}
+// the per-item pairing checks of items [lo, lo + m): every item's own final exponentiation
+void pair_per_item(hipStream_t s0, const CallBufs& B, size_t lo, size_t m) {
+    const BlsEnv& env = bls_env();
+    if (env.pack > 1)
+        hipLaunchKernelGGL(k_blsw_pair_k, dim3((unsigned)((m + env.pack - 1) / env.pack)), dim3(64), pack_lds(env), s0,
+                           (uint32_t)m, env.pack, B.srec + G1_REC_WORDS * lo, B.sdec + lo, B.hrec + G1_REC_WORDS * lo, 0,
+                           B.ajrec + G2J_WORDS * lo, B.sapk + lo, B.kt, B.off + lo, B.cnt + lo, B.idx,
+                           B.km ? B.km + lo : nullptr, B.spair + lo);
+    else
+        hipLaunchKernelGGL(k_blsw_pair, dim3((unsigned)m), dim3(64), env.lds_pad, s0, (uint32_t)m,
+                           B.srec + G1_REC_WORDS * lo, B.sdec + lo, B.hrec + G1_REC_WORDS * lo, 0,
+                           B.ajrec + G2J_WORDS * lo, B.sapk + lo, B.kt, B.off + lo, B.cnt + lo, B.idx,
+                           B.km ? B.km + lo : nullptr, B.spair + lo);
+}
+// The per-item launches behind a batch check's rejected groups (need[i] != 0).  A launch over a few
+// items costs one item's whole chain (~3 ms) however few they are, so marked items less than
+// RECHECK_GAP items apart share a launch with the accepted items between them (~1 us an item
+// there).  Returns the items the launches covered.
+constexpr size_t RECHECK_GAP = 1024;
+template <class Fn>
+void pair_recheck(hipStream_t s0, const CallBufs& B, const std::vector<uint8_t>& need, Fn per_range) {
+    for (const auto& r : nwv::recheck_ranges(B.n, need.data(), RECHECK_GAP)) {
+        pair_per_item(s0, B, r.first, r.second - r.first);
+        per_range(r.first, r.second);
     }
-    // main: signatures, then the join
+}
+
+// The key-transposed check (paths 6 and 7).  *done = false when its plan does not run: the call
+// then takes the stage it takes with the setting off.
+int pair_key_batch(BlsDev& d, BlsLane& L, const CallPlan& P, const CallBufs& B, const CallIn& c, CallStats& T,
+                   bool* done) {
+    const BlsEnv& env = bls_env();
+    const size_t n = c.n;
+    const hipStream_t s0 = L.stream;
+    int rc;
+    *done = false;
+    // the pre-pairing statuses come back first: the plan groups the items they leave
+    if ((rc = L.kb_st.ensure(12 * n + 64))) return rc;
+    int32_t* h_dec = static_cast<int32_t*>(L.kb_st.p);
+    int32_t *h_apk = h_dec + n, *h_gok = h_apk + n;
+    BLS_HIP(hipMemcpyAsync(h_dec, B.sdec, 4 * n, hipMemcpyDeviceToHost, s0));
+    BLS_HIP(hipMemcpyAsync(h_apk, B.sapk, 4 * n, hipMemcpyDeviceToHost, s0));
+    BLS_HIP(hipStreamSynchronize(s0));
+    std::vector<uint8_t> ok(n), el(n);
+    for (size_t i = 0; i < n; i++) {
+        ok[i] = h_dec[i] == ST_OK && h_apk[i] == ST_OK;
+        // (a compressed identity has bit 6 of its first byte set; the kernels check again)
+        el[i] = ok[i] && P.kmode[i] && !(c.sigs[48 * i] & 0x40);
+    }
+    nwv::KeyBatchPlan K;
+    nwv::key_batch_plan(n, ok.data(), el.data(), c.pk_off, c.pk_cnt, P.remap.data(), d.kc.used, env.kb_grp,
+                        env.kb_ratio, K);
+    if (!K.run) return NWV_OK;
+    const size_t ne = K.items.size(), ng = K.groups(), M = K.entries(), C = K.cidx.size(), KM = M + ng;
+    // the plan's lists, one copy: items | goff | eslot | egrp | coff | cidx | 0..M-1 | ones
+    Layout u;
+    const auto u_items = u.packed<uint32_t>(4 * ne), u_goff = u.packed<uint32_t>(4 * (ng + 1)),
+               u_eslot = u.packed<uint32_t>(4 * M), u_egrp = u.packed<uint32_t>(4 * M),
+               u_coff = u.packed<uint32_t>(4 * (M + 1)), u_cidx = u.packed<uint32_t>(4 * C),
+               u_iota = u.packed<uint32_t>(4 * M), u_ones = u.packed<uint32_t>(4 * M);
+    if ((rc = L.kb_up.ensure(u.end)) || (rc = L.kb_in.ensure(u.end))) return rc;
+    void* up = L.kb_up.p;
+    std::memcpy(u_items.at(up), K.items.data(), 4 * ne);
+    std::memcpy(u_goff.at(up), K.goff.data(), 4 * (ng + 1));
+    std::memcpy(u_eslot.at(up), K.eslot.data(), 4 * M);
+    std::memcpy(u_egrp.at(up), K.egrp.data(), 4 * M);
+    std::memcpy(u_coff.at(up), K.coff.data(), 4 * (M + 1));
+    std::memcpy(u_cidx.at(up), K.cidx.data(), 4 * C);
+    for (size_t m = 0; m < M; m++) {
+        u_iota.at(up)[m] = (uint32_t)m;
+        u_ones.at(up)[m] = 1u;
+    }
+    void* ki = L.kb_in.p;
+    BLS_HIP(hipMemcpyAsync(ki, up, u.end, hipMemcpyHostToDevice, s0));
+    const uint32_t *items = u_items.at(ki), *eslot = u_eslot.at(ki), *ones = u_ones.at(ki);
+    // the check's records: [r] H and [r] sig per position, S_g per group, the Miller
+    // entries' hash sides, Qs and F records, the groups' poison and verdict words
+    Layout k;
+    const auto k_hj = k.aligned<uint32_t>(4 * G1J_REC_WORDS * ne), k_sj = k.aligned<uint32_t>(4 * G1J_REC_WORDS * ne),
+               k_sg = k.aligned<uint32_t>(4 * G1_REC_WORDS * ng), k_p = k.aligned<uint32_t>(4 * G1H_REC_WORDS * KM),
+               k_q = k.aligned<uint32_t>(4 * G2J_WORDS * KM), k_f = k.aligned<uint32_t>(4 * FB_REC_WORDS * KM),
+               k_poi = k.aligned<uint32_t>(4 * ng);
+    const auto k_gok = k.packed<int32_t>(4 * ng + 4);
+    if ((rc = L.kb_work.ensure(k.end))) return rc;
+    void* kw = L.kb_work.p;
+    uint32_t *khj = k_hj.at(kw), *ksj = k_sj.at(kw), *ksg = k_sg.at(kw), *kp = k_p.at(kw), *kq = k_q.at(kw),
+             *kf = k_f.at(kw), *kpoi = k_poi.at(kw);
+    int32_t* kgok = k_gok.at(kw);
+    const uint32_t G = env.kb_grp, gmax = (uint32_t)std::min<size_t>(G, ne);
+    uint32_t kmax = 0;
+    for (size_t g = 0; g < ng; g++) kmax = std::max(kmax, K.goff[g + 1] - K.goff[g]);
+    BLS_HIP(hipMemsetAsync(kpoi, 0, 8 * ng, s0));  // no poison; a group whose tree does not finish stays rejected
+    hipLaunchKernelGGL(k_blsk_rlc_pts, dim3(kBlocks(2 * ne)), dim3(BLS_LANES), 0, s0, (uint32_t)ne, G, items, B.srec,
+                       B.hrec, B.sdec, B.sapk, B.seed, khj, ksj, kpoi);
+    for (uint32_t m = gmax; m > 1; m = (m + 1) / 2)
+        hipLaunchKernelGGL(k_blsw_sfold, dim3(kBlocks(ng * ((m + 1) / 2))), dim3(BLS_LANES), 0, s0, (uint32_t)ne, G,
+                           (uint32_t)ng, m, ksj);
+    hipLaunchKernelGGL(k_blsk_key_sums, dim3((unsigned)M), dim3(64), 0, s0, (uint32_t)M, u_coff.at(ki), u_cidx.at(ki),
+                       eslot, u_egrp.at(ki), khj, B.kt, kp, kq, kpoi);
+    hipLaunchKernelGGL(k_blsk_sig_items, dim3(kBlocks(ng)), dim3(BLS_LANES), 0, s0, (uint32_t)ng, G, (uint32_t)M, ksj,
+                       ksg, kp, kq);
+    // every key entry as a one-key key-side item of its own: key list entry m = slot eslot[m]
+    const MillArgs ma{(uint32_t)M, ksg, ones, kf};
+    hipLaunchKernelGGL(k_blsw_mill_k, dim3((unsigned)((KM + env.pack - 1) / env.pack)), dim3(64), pack_lds(env), s0,
+                       (uint32_t)KM, env.pack, ma, kp, kq, B.kt, u_iota.at(ki), ones, eslot, ones);
+    for (uint32_t s = 1;; s *= WB_FAN) {
+        const uint32_t ents = (kmax + 1 + s - 1) / s, wpg = (ents + WB_FAN - 1) / WB_FAN;
+        hipLaunchKernelGGL(k_blsk_ffold, dim3((unsigned)(ng * wpg)), dim3(64), 0, s0, (uint32_t)ng, u_goff.at(ki),
+                           (uint32_t)M, wpg, s, wpg == 1 ? 1 : 0, kf, kpoi, kgok);
+        if (wpg == 1) break;
+    }
+    hipLaunchKernelGGL(k_blsk_mark, dim3(kBlocks(ne)), dim3(BLS_LANES), 0, s0, (uint32_t)ne, G, items, kgok, B.spair);
+    BLS_HIP(hipGetLastError());
+    BLS_HIP(hipMemcpyAsync(h_gok, kgok, 4 * ng, hipMemcpyDeviceToHost, s0));
+    BLS_HIP(hipStreamSynchronize(s0));
+    // per item: the OK items outside the groups and every rejected group's items
+    std::vector<uint8_t> need(n, 0), ing(n, 0);
+    for (uint32_t i : K.outside) need[i] = 1;
+    for (uint32_t i : K.items) ing[i] = 1;
+    for (size_t g = 0; g < ng; g++) {
+        if (h_gok[g] == 1) continue;
+        T.kb[1]++;
+        for (uint32_t p = K.gfirst[g]; p < K.gfirst[g + 1]; p++) need[K.items[p]] = 1;
+    }
+    pair_recheck(s0, B, need, [&](size_t lo, size_t hi) {
+        for (size_t i = lo; i < hi; i++) T.kb[2] += ing[i];
+    });
+    T.kb[0] = ng;
+    T.kb[3] = KM;
+    T.kb[4] = ne;
+    T.path = T.kb[1] ? 7 : 6;
+    *done = true;
+    return NWV_OK;
+}
+
+// The wave batch check (paths 4 and 5): one final exponentiation per group of wb_grp items, then
+// every rejected group's items per item
+int pair_wave_batch(BlsLane& L, const CallPlan& P, const CallBufs& B, CallStats& T) {
+    const BlsEnv& env = bls_env();
+    const size_t n = B.n;
+    const hipStream_t s0 = L.stream;
+    const uint32_t G = (uint32_t)env.wb_grp, ng = (uint32_t)P.wb_ng, gmax = (uint32_t)std::min<size_t>(env.wb_grp, n);
+    BLS_HIP(hipMemsetAsync(B.wgok, 0, 4 * P.wb_ng, s0));  // a group whose tree does not finish stays rejected
+    hipLaunchKernelGGL(k_blsw_rlc_pts, dim3(kBlocks(2 * n)), dim3(BLS_LANES), 0, s0, (uint32_t)n, B.srec, B.hrec, B.sdec,
+                       B.sapk, B.km, B.seed, B.wp, B.wj, B.winb, B.spair);
+    for (uint32_t m = gmax; m > 1; m = (m + 1) / 2)
+        hipLaunchKernelGGL(k_blsw_sfold, dim3(kBlocks((size_t)ng * ((m + 1) / 2))), dim3(BLS_LANES), 0, s0, (uint32_t)n,
+                           G, ng, m, B.wj);
+    hipLaunchKernelGGL(k_blsw_sig_items, dim3(kBlocks(ng)), dim3(BLS_LANES), 0, s0, (uint32_t)n, G, ng, B.wj, B.wsg,
+                       B.wp, B.ajrec);
+    const MillArgs ma{(uint32_t)n, B.wsg, B.winb, B.wf};
+    hipLaunchKernelGGL(k_blsw_mill_k, dim3((unsigned)((P.wb_m + env.pack - 1) / env.pack)), dim3(64), pack_lds(env), s0,
+                       (uint32_t)P.wb_m, env.pack, ma, B.wp, B.ajrec, B.kt, B.off, B.cnt, B.idx, B.km);
+    for (uint32_t s = 1;; s *= WB_FAN) {
+        const uint32_t ents = (gmax + 1 + s - 1) / s, wpg = (ents + WB_FAN - 1) / WB_FAN;
+        hipLaunchKernelGGL(k_blsw_ffold, dim3(ng * wpg), dim3(64), 0, s0, (uint32_t)n, G, wpg, s, wpg == 1 ? 1 : 0,
+                           B.wf, B.wgok);
+        if (wpg == 1) break;
+    }
+    hipLaunchKernelGGL(k_blsw_mark, dim3(kBlocks(n)), dim3(BLS_LANES), 0, s0, (uint32_t)n, G, B.wgok, B.winb, B.spair);
+    BLS_HIP(hipGetLastError());
+    BLS_HIP(hipMemcpyAsync(B.h_gok, B.wgok, 4 * P.wb_ng, hipMemcpyDeviceToHost, s0));
+    BLS_HIP(hipStreamSynchronize(s0));
+    std::vector<uint8_t> need(n, 0);
+    T.wb[0] = P.wb_ng;
+    for (size_t g = 0; g < P.wb_ng; g++) {
+        if (B.h_gok[g] == 1) continue;
+        T.wb[1]++;
+        std::fill(need.begin() + g * env.wb_grp, need.begin() + std::min(n, (g + 1) * env.wb_grp), 1);
+    }
+    pair_recheck(s0, B, need, [&](size_t lo, size_t hi) { T.wb[2] += hi - lo; });
+    T.path = T.wb[1] ? 5 : 4;
+    return NWV_OK;
+}
+
+// The large wave call: the one-lane-per-item decode + G1 check of the group path, which keeps every
+// lane busy (an all-Ok subgroup column), then every item's pairing check on a wave by one of three
+// stages: the key-transposed check, the wave batch check, or per item (path 3)
+int run_large_wave(BlsDev& d, BlsLane& L, const CallPlan& P, const CallBufs& B, const CallIn& c, int32_t* status,
+                   CallStats& T) {
+    const size_t n = c.n, n_dn = P.ads.dense.size();
+    const hipStream_t s0 = L.stream;
+    int rc = large_sides(L, P, B, c);
+    if (rc) return rc;
     BLS_HIP(hipEventRecord(L.ev[3], s0));
-    hipLaunchKernelGGL(k_bls_sigs, dim3(kBlocks(n)), dim3(BLS_LANES), 0, s0, (uint32_t)n, in + o_sigs, srec, ssig);
+    hipLaunchKernelGGL(k_bls_sigs, dim3(kBlocks(n)), dim3(BLS_LANES), 0, s0, (uint32_t)n, B.sigs, B.srec, B.sdec);
+    BLS_HIP(hipMemsetAsync(B.ssub, 0, 4 * n, s0));
     BLS_HIP(hipEventRecord(L.ev[4], s0));
     BLS_HIP(hipStreamWaitEvent(s0, L.ev[10], 0));
     BLS_HIP(hipStreamWaitEvent(s0, L.ev[11], 0));
-    hipLaunchKernelGGL(k_bls_status, dim3(kBlocks(n)), dim3(BLS_LANES), 0, s0, (uint32_t)n, (const int32_t*)ssig,
-                       (const int32_t*)sapk, st);
     BLS_HIP(hipEventRecord(L.ev[7], s0));
-    auto per_item = [&]() {
-        hipLaunchKernelGGL(k_bls_pair, dim3(gBlocks(n)), dim3(BLS_LANES), 0, s0, (uint32_t)n, (const uint32_t*)srec,
-                           (const uint32_t*)hrec, (const uint32_t*)arec, st);
-    };
-    int32_t* hst = reinterpret_cast<int32_t*>(h + al256(a.total));  // pinned: the batch verdict word
-    int path;
-    if (batch) {
-        hipLaunchKernelGGL(k_bls_rlc_pts, dim3(gBlocks(n)), dim3(BLS_LANES), 0, s0, (uint32_t)n, (const uint32_t*)srec,
-                           (const uint32_t*)hrec, (const int32_t*)st, (const uint8_t*)(in + o_seed), prec, jrec);
-        for (uint32_t m = (uint32_t)n; m > 1; m = (m + 1) / 2)
-            hipLaunchKernelGGL(k_bls_sfold, dim3(kBlocks(m / 2)), dim3(BLS_LANES), 0, s0, m, jrec);
-        hipLaunchKernelGGL(k_bls_sig_item, dim3(1), dim3(BLS_LANES), 0, s0, (uint32_t)n, (const uint32_t*)jrec, prec,
-                           arec);
-        hipLaunchKernelGGL(k_bls_rlc_ml, dim3(gBlocks(n + 1)), dim3(BLS_LANES), 0, s0, (uint32_t)(n + 1),
-                           (const uint32_t*)prec, (const uint32_t*)arec, frec);
-        for (uint32_t m = (uint32_t)n + 1; m > 1; m = (m + 1) / 2)
-            hipLaunchKernelGGL(k_bls_ffold, dim3(gBlocks(m / 2)), dim3(BLS_LANES), 0, s0, m, frec);
-        hipLaunchKernelGGL(k_bls_final, dim3(1), dim3(BLS_LANES), 0, s0, (const uint32_t*)frec, okw);
-        BLS_HIP(hipMemcpyAsync(hst, okw, 4, hipMemcpyDeviceToHost, s0));
-        BLS_HIP(hipStreamSynchronize(s0));
-        BLS_HIP(hipGetLastError());
-        path = *hst == 1 ? 1 : 2;
-        if (*hst != 1) per_item();  // the batch check rejected: name the failing items exactly
-    } else {
-        per_item();
-        path = 0;
+    if ((bls_env().pack > 1 || P.wbatch || P.kb_cand) && ensure_pair_script()) return NWV_ERR_HIP;
+    T.path = 3;
+    bool kb_done = false;
+    if (P.kb_cand && (rc = pair_key_batch(d, L, P, B, c, T, &kb_done))) return rc;
+    if (!kb_done && P.wbatch) {
+        if ((rc = pair_wave_batch(L, P, B, T))) return rc;
+    } else if (!kb_done) {
+        pair_per_item(s0, B, 0, n);
     }
     BLS_HIP(hipEventRecord(L.ev[8], s0));
-    BLS_HIP(hipGetLastError());
-    BLS_HIP(hipMemcpyAsync(status, st, 4 * n, hipMemcpyDeviceToHost, s0));
-    BLS_HIP(hipStreamSynchronize(s0));
-    return finish(path);
+    if ((rc = wave_status_back(s0, B, status, nullptr, B.h_dmode, B.dmode, 4 * n_dn))) return rc;
+    if (P.ad_run) {
+        for (size_t q = 0; q < n_dn; q++) T.ad[B.h_dmode[q] ? 1 : 0]++;
+        T.ad[2] = P.ads.rest.size();
+        T.ad[3] = P.ad_lanes;
+    }
+    return NWV_OK;
+}
+
+// The group engines (8 lanes an item): per item (path 0), or one batch check over the call (path 1)
+// and per item only when that rejects (path 2)
+int run_group(BlsLane& L, const CallPlan& P, const CallBufs& B, const CallIn& c, int32_t* status, CallStats& T) {
+    const size_t n = c.n;
+    const hipStream_t s0 = L.stream;
+    int rc = large_sides(L, P, B, c);
+    if (rc) return rc;
+    // main: signatures, then the join
+    BLS_HIP(hipEventRecord(L.ev[3], s0));
+    hipLaunchKernelGGL(k_bls_sigs, dim3(kBlocks(n)), dim3(BLS_LANES), 0, s0, (uint32_t)n, B.sigs, B.srec, B.ssig);
+    BLS_HIP(hipEventRecord(L.ev[4], s0));
+    BLS_HIP(hipStreamWaitEvent(s0, L.ev[10], 0));
+    BLS_HIP(hipStreamWaitEvent(s0, L.ev[11], 0));
+    hipLaunchKernelGGL(k_bls_status, dim3(kBlocks(n)), dim3(BLS_LANES), 0, s0, (uint32_t)n, B.ssig, B.sapk, B.st);
+    BLS_HIP(hipEventRecord(L.ev[7], s0));
+    auto per_item = [&]() {
+        hipLaunchKernelGGL(k_bls_pair, dim3(gBlocks(n)), dim3(BLS_LANES), 0, s0, (uint32_t)n, B.srec, B.hrec, B.arec,
+                           B.st);
+    };
+    if (P.batch) {
+        hipLaunchKernelGGL(k_bls_rlc_pts, dim3(gBlocks(n)), dim3(BLS_LANES), 0, s0, (uint32_t)n, B.srec, B.hrec, B.st,
+                           B.seed, B.prec, B.jrec);
+        for (uint32_t m = (uint32_t)n; m > 1; m = (m + 1) / 2)
+            hipLaunchKernelGGL(k_bls_sfold, dim3(kBlocks(m / 2)), dim3(BLS_LANES), 0, s0, m, B.jrec);
+        hipLaunchKernelGGL(k_bls_sig_item, dim3(1), dim3(BLS_LANES), 0, s0, (uint32_t)n, B.jrec, B.prec, B.arec);
+        hipLaunchKernelGGL(k_bls_rlc_ml, dim3(gBlocks(n + 1)), dim3(BLS_LANES), 0, s0, (uint32_t)(n + 1), B.prec, B.arec,
+                           B.frec);
+        for (uint32_t m = (uint32_t)n + 1; m > 1; m = (m + 1) / 2)
+            hipLaunchKernelGGL(k_bls_ffold, dim3(gBlocks(m / 2)), dim3(BLS_LANES), 0, s0, m, B.frec);
+        hipLaunchKernelGGL(k_bls_final, dim3(1), dim3(BLS_LANES), 0, s0, B.frec, B.okw);
+        BLS_HIP(hipMemcpyAsync(B.h_ok, B.okw, 4, hipMemcpyDeviceToHost, s0));
+        BLS_HIP(hipStreamSynchronize(s0));
+        BLS_HIP(hipGetLastError());
+        T.path = *B.h_ok == 1 ? 1 : 2;
+        if (*B.h_ok != 1) per_item();  // the batch check rejected: name the failing items exactly
+    } else {
+        per_item();
+        T.path = 0;
+    }
+    BLS_HIP(hipEventRecord(L.ev[8], s0));
+    return copy_back(s0, B, status);
+}
+
+// stage times of the completed call, its path and key counts -> the device's "last call"
+int record_last(BlsDev& d, BlsLane& L, const CallPlan& P, const CallStats& T) {
+    const int pairs[5][2] = {{0, 1}, {3, 4}, {5, 6}, {1, 2}, {7, 8}};  // keys, sigs, h2c, apk, pairing
+    double ms5[5] = {0, 0, 0, 0, 0};
+    for (int k = 0; k < 5 && !T.untimed; k++) {
+        float ms = 0;
+        BLS_HIP(hipEventElapsedTime(&ms, L.ev[pairs[k][0]], L.ev[pairs[k][1]]));
+        ms5[k] = ms;
+    }
+    std::lock_guard<std::mutex> g(d.stat_mu);
+    std::memcpy(d.last_ms, ms5, sizeof ms5);
+    d.last_path = T.path;
+    d.last_keys[0] = P.hits;
+    d.last_keys[1] = P.n_dec();
+    std::memcpy(d.last_batch, T.wb, sizeof T.wb);
+    std::memcpy(d.last_kbatch, T.kb, sizeof T.kb);
+    std::memcpy(d.last_apkd, T.ad, sizeof T.ad);
+    return NWV_OK;
+}
+
+// nwv_bls_verify_many on one lane of a device: lease, plan, buffers, one H2D copy, the path's
+// function, the bookkeeping
+int verify_on(BlsDev& d, const CallIn& c, int32_t* status, const Ahead* ahead = nullptr, uint64_t* mstat = nullptr,
+              uint64_t* astat = nullptr, bool latency = false) {
+    // (declaration order is a condition, see CallSlots: destroyed in reverse, the ring slots go
+    // back before the key-cache lock drops and before the lane returns to the pool)
+    LaneLease lane(d, latency);
+    if (lane.rc()) return lane.rc();
+    BlsLane& L = *lane;
+    std::shared_lock<std::shared_mutex> kc_hold(d.kc.mu);  // records stay put while our kernels read them
+    CallSlots S;
+    CallPlan P;
+    int rc = plan_call(d, L, c, ahead, S, P);
+    if (rc) return rc;
+    static const uint8_t zero[8] = {0};
+    const size_t n = c.n, n_dec = P.n_dec(), nk_idx = P.k_idx->size(), n_dn = P.ads.dense.size(),
+                 n_rest = P.ads.rest.size();
+    uint8_t seed[32];
+    nwv_internal_fill_seed(nullptr, seed);  // the batch coefficients' key: OS entropy per call
+    Arena a;
+    const auto o_keys = a.add<uint8_t>(n_dec ? (const void*)P.fill_keys.data() : zero, 96 * n_dec + 8);
+    const auto o_kslot = a.add<uint32_t>(n_dec ? (const void*)P.fill_slot.data() : zero, 4 * n_dec + 4);
+    const auto o_sigs = a.add<uint8_t>(c.sigs, 48 * n);
+    const auto o_off = a.add<uint32_t>(P.k_off, 4 * n), o_cnt = a.add<uint32_t>(P.k_cnt, 4 * n),
+               o_idx = a.add<uint32_t>(nk_idx ? (const void*)P.k_idx->data() : zero, 4 * nk_idx + 4);
+    const auto o_msg = a.add<uint8_t>(c.msg_bytes ? (const void*)c.msg_base : zero, c.msg_bytes + 1);
+    const auto o_moff = a.add<uint64_t>(c.msg_off, 8 * n);
+    const auto o_mlen = a.add<uint32_t>(c.msg_len, 4 * n);
+    const auto o_dst = a.add<uint8_t>(c.dst, c.dl), o_seed = a.add<uint8_t>(seed, 32);
+    const auto o_kmode = a.add<uint32_t>(P.kside ? (const void*)P.kmode.data() : zero, 4 * P.kmode.size() + 4),
+               o_scs = a.add<uint32_t>(P.keep ? (const void*)S.kept.slots.data() : zero, 4 * S.kept.slots.size() + 4);
+    // (one section for everything the ring adds: a single verification still fits stage_h2d's arguments)
+    const auto o_ring = P.use_ring ? a.add<uint8_t>(P.rsec.data(), P.rsec.size()) : Sec<const uint8_t>{};
+    const auto o_fill = P.n_fill ? a.add<uint32_t>(P.a_fill.data(), 8 * P.n_fill) : Sec<const uint32_t>{};
+    const auto o_dlist = n_dn ? a.add<uint32_t>(P.ads.dense.data(), 4 * n_dn) : Sec<const uint32_t>{},
+               o_rlist = n_dn && n_rest ? a.add<uint32_t>(P.ads.rest.data(), 4 * n_rest) : Sec<const uint32_t>{},
+               o_idx0 = n_dn ? a.add<uint32_t>(c.pk_idx, 4 * c.n_idx) : Sec<const uint32_t>{},
+               o_ktab = n_dn ? a.add<uint32_t>(P.ktab.data(), 4 * c.n_keys) : Sec<const uint32_t>{};
+    // (pinned, behind the arena: the batch verdict word, the wave batch check's group verdicts, the
+    // dense key sums' per-item modes)
+    const size_t h_dmode = al256(al256(a.total) + 64 + 4 * P.wb_ng);
+    if ((rc = L.stage.ensure(h_dmode + 4 * n_dn)) || (rc = L.in.ensure(a.total))) return rc;
+    uint8_t* h = static_cast<uint8_t*>(L.stage.p);
+    a.fill(h);
+    // scratch: the call's key records + statuses, then CallBufs's sections in its order
+    const bool batch = P.batch, wavem = P.wavem;
+    Layout w;
+    const auto w_krec = w.packed<uint32_t>(4 * G2_REC_WORDS * n_dec);
+    const auto w_kst = w.packed<int32_t>(4 * n_dec + 4);
+    const auto w_srec = w.aligned<uint32_t>(4 * G1_REC_WORDS * n), w_hrec = w.packed<uint32_t>(4 * G1_REC_WORDS * n),
+               w_arec = w.packed<uint32_t>(4 * G2_REC_WORDS * (n + 1));
+    const auto w_st = w.packed<int32_t>(4 * n), w_ssig = w.aligned<int32_t>(4 * n), w_sapk = w.aligned<int32_t>(4 * n),
+               w_ok = w.aligned<int32_t>(4);
+    const auto w_frec = w.aligned<uint32_t>(4 * F12_REC_WORDS * (batch ? n + 1 : 0)),
+               w_jrec = w.aligned<uint32_t>(4 * G1J_REC_WORDS * (batch ? n : 0)),
+               w_prec = w.aligned<uint32_t>(4 * G1J_REC_WORDS * (batch ? n + 1 : 0) + 4),
+               w_hh = w.aligned<uint32_t>(4 * G1H_REC_WORDS * (wavem ? n : 0));
+    const auto w_sdec = w.aligned<int32_t>(4 * n), w_ssub = w.aligned<int32_t>(4 * n),
+               w_spair = w.aligned<int32_t>(4 * n + 4);
+    const auto w_aj = w.aligned<uint32_t>(4 * G2J_WORDS * (wavem ? n + P.wb_ng : 0) + 4),
+               w_wf = w.aligned<uint32_t>(4 * FB_REC_WORDS * P.wb_m), w_wp = w.aligned<uint32_t>(4 * G1H_REC_WORDS * P.wb_m),
+               w_wj = w.aligned<uint32_t>(4 * G1J_REC_WORDS * (P.wbatch ? n : 0)),
+               w_wsg = w.aligned<uint32_t>(4 * G1_REC_WORDS * P.wb_ng), w_winb = w.aligned<uint32_t>(4 * (P.wbatch ? n : 0));
+    const auto w_wgok = w.aligned<int32_t>(4 * P.wb_ng + 4);
+    const auto w_dtot = w.aligned<uint32_t>(4 * (n_dn ? DT_WORDS : 0)), w_dmode = w.aligned<uint32_t>(4 * n_dn + 4);
+    if ((rc = L.work.ensure(w.end))) return rc;
+    void* in = L.in.p;
+    void* wk = L.work.p;
+    const bool lines = P.cached && d.kc.lines_slots;
+    CallBufs B;
+    B.n = n;
+    B.dl = c.dl;
+    B.keys = o_keys.at(in), B.sigs = o_sigs.at(in), B.msg = o_msg.at(in), B.dst = o_dst.at(in), B.seed = o_seed.at(in);
+    B.kslot = o_kslot.at(in), B.off = o_off.at(in), B.cnt = o_cnt.at(in), B.idx = o_idx.at(in), B.mlen = o_mlen.at(in);
+    B.moff = o_moff.at(in);
+    B.km = P.kside ? o_kmode.at(in) : nullptr;
+    B.scs = o_scs.at(in);
+    const uint8_t* ring = o_ring.at(in);
+    B.aoff = Sec<uint64_t>{o_ring.off}.at(in);
+    B.hsrc = Sec<uint32_t>{o_ring.off + P.r_hsrc}.at(in), B.hpub = Sec<uint32_t>{o_ring.off + P.r_hpub}.at(in);
+    B.aslot = Sec<uint32_t>{o_ring.off + P.r_aslot}.at(in), B.alen = Sec<uint32_t>{o_ring.off + P.r_alen}.at(in);
+    B.amsg = ring + P.r_amsg;
+    B.fill_item = o_fill.at(in), B.fill_slot = o_fill.at(in) + P.n_fill;
+    B.dlist = o_dlist.at(in), B.rlist = o_rlist.at(in), B.idx0 = o_idx0.at(in), B.ktab = o_ktab.at(in);
+    B.srec = w_srec.at(wk), B.hrec = w_hrec.at(wk), B.arec = w_arec.at(wk), B.frec = w_frec.at(wk);
+    B.jrec = w_jrec.at(wk), B.prec = w_prec.at(wk), B.hh = w_hh.at(wk), B.ajrec = w_aj.at(wk);
+    B.st = w_st.at(wk), B.ssig = w_ssig.at(wk), B.sapk = w_sapk.at(wk), B.okw = w_ok.at(wk);
+    B.sdec = w_sdec.at(wk), B.ssub = w_ssub.at(wk), B.spair = w_spair.at(wk);
+    B.wf = w_wf.at(wk), B.wp = w_wp.at(wk), B.wj = w_wj.at(wk), B.wsg = w_wsg.at(wk), B.winb = w_winb.at(wk);
+    B.wgok = w_wgok.at(wk);
+    B.dtot = w_dtot.at(wk), B.dmode = w_dmode.at(wk);
+    B.kt = KeyTab{P.cached ? static_cast<const uint32_t*>(d.kc.rec.p) : nullptr,
+                  P.cached ? static_cast<const int32_t*>(d.kc.st.p) : nullptr,
+                  w_krec.at(wk),
+                  w_kst.at(wk),
+                  lines ? static_cast<const uint32_t*>(d.kc.lines.p) : nullptr,
+                  P.cached ? static_cast<const uint32_t*>(d.kc.hrec.p) : nullptr,
+                  P.use_apk ? static_cast<const uint32_t*>(d.ar.rec.p) : nullptr,
+                  P.use_apk ? static_cast<const uint32_t*>(d.ar.lines.p) : nullptr};
+    B.h_ok = Sec<int32_t>{al256(a.total)}.at(h), B.h_gok = Sec<int32_t>{al256(a.total) + 64}.at(h);
+    B.h_dmode = Sec<uint32_t>{h_dmode}.at(h);
+    const hipStream_t s0 = L.stream;
+    S.kept.stream = s0;
+    BLS_HIP(nwv_stage::stage_h2d(in, h, a.total, s0));  // small calls: through kernel arguments
+    BLS_HIP(hipEventRecord(L.sev[0], s0));
+    BLS_HIP(hipStreamWaitEvent(L.side[0], L.sev[0], 0));
+    CallStats T;
+    if (P.wave_small) rc = run_small(d, L, P, B, c, status, S, mstat, astat, T);
+    else if (P.wavem) rc = run_large_wave(d, L, P, B, c, status, T);
+    else rc = run_group(L, P, B, c, status, T);
+    return rc ? rc : record_last(d, L, P, T);
 }
 
 // nwv_bls_hash_ahead on one device: the messages the ring does not hold, hashed (raw) into reserved
@@ -2606,11 +2741,9 @@ int msg_ring_fill(BlsDev& d, size_t n, const uint8_t* base, const uint64_t* off,
         MsgSlots ms;
         ms.ring = &R;
         ms.streams[0] = L.stream;
-        std::vector<uint32_t> aslot, alen;
-        std::vector<uint64_t> aoff;
-        std::vector<uint8_t> amsg;
+        AheadPack ap;
         size_t j = j0;
-        for (; j < n && aslot.size() < chunk; j++) {
+        for (; j < n && ap.n() < chunk; j++) {
             if ((sel && !sel[j]) || len[j] > nwv::MsgKey::MAX_MSG) continue;
             const nwv::MsgKey k = nwv::MsgKey::make(dst, dl, base + off[j], len[j]);
             if (R.contains(k)) continue;
@@ -2620,29 +2753,22 @@ int msg_ring_fill(BlsDev& d, size_t n, const uint8_t* base, const uint64_t* off,
             const uint32_t r = R.reserve();
             if (r == nwv::BlsMsgRing::NONE) continue;  // every slot in use by calls in flight
             ms.fresh.push_back({r, k, UINT32_MAX, true});
-            aslot.push_back(r);
-            alen.push_back(len[j]);
-            aoff.push_back(amsg.size());
-            amsg.insert(amsg.end(), base + off[j], base + off[j] + len[j]);
+            ap.push(r, base + off[j], len[j]);
         }
         j0 = j;
-        const size_t m = aslot.size();
+        const size_t m = ap.n();
         if (!m) continue;
-        const size_t o_slot = 8 * m, o_len = o_slot + 4 * m, o_dst = o_len + 4 * m, o_msg = o_dst + al256(dl + 1),
-                     total = o_msg + amsg.size() + 1;
-        if ((rc = L.stage.ensure(total)) || (rc = L.in.ensure(total))) return rc;
-        uint8_t* h = static_cast<uint8_t*>(L.stage.p);
-        uint8_t* in = static_cast<uint8_t*>(L.in.p);
-        std::memcpy(h, aoff.data(), 8 * m);
-        std::memcpy(h + o_slot, aslot.data(), 4 * m);
-        std::memcpy(h + o_len, alen.data(), 4 * m);
-        std::memcpy(h + o_dst, dst, dl);
-        if (!amsg.empty()) std::memcpy(h + o_msg, amsg.data(), amsg.size());
-        BLS_HIP(nwv_stage::stage_h2d(in, h, total, L.stream));
-        hipLaunchKernelGGL(k_blsw_h2c_ahead, dim3((unsigned)m), dim3(64), 0, L.stream, (uint32_t)m,
-                           (const uint8_t*)(in + o_msg), reinterpret_cast<const uint64_t*>(in),
-                           reinterpret_cast<const uint32_t*>(in + o_len), (const uint8_t*)(in + o_dst), (uint32_t)dl,
-                           static_cast<uint32_t*>(d.mr.rec.p), reinterpret_cast<const uint32_t*>(in + o_slot));
+        Layout o;
+        const auto o_off = o.packed<uint64_t>(8 * m);
+        const auto o_slot = o.packed<uint32_t>(4 * m), o_len = o.packed<uint32_t>(4 * m);
+        const auto o_dst = o.packed<uint8_t>(al256(dl + 1)), o_msg = o.packed<uint8_t>(ap.msg.size() + 1);
+        if ((rc = L.stage.ensure(o.end)) || (rc = L.in.ensure(o.end))) return rc;
+        void* h = L.stage.p;
+        void* in = L.in.p;
+        ap.write(h, o_slot.at(h), o_len.at(h), o_msg.at(h));
+        std::memcpy(o_dst.at(h), dst, dl);
+        BLS_HIP(nwv_stage::stage_h2d(in, h, o.end, L.stream));
+        launch_ahead(L.stream, m, o_msg.at(in), o_off.at(in), o_len.at(in), o_dst.at(in), dl, d.mr.rec.p, o_slot.at(in));
         BLS_HIP(hipGetLastError());
         BLS_HIP(hipStreamSynchronize(L.stream));
         ms.finish(nullptr, nullptr);
@@ -2650,14 +2776,29 @@ int msg_ring_fill(BlsDev& d, size_t n, const uint8_t* base, const uint64_t* off,
     return NWV_OK;
 }
 
-// a call splits over the devices only into ranges of at least this many items (env
-// NWV_BLS_SHARD_MIN, read once)
-size_t bls_shard_min() {
-    static const size_t v = [] {
-        const char* e = std::getenv("NWV_BLS_SHARD_MIN");
-        return e ? (size_t)std::strtoull(e, nullptr, 10) : (size_t)256;
-    }();
-    return v;
+// a per-device threshold of the context (nwv_bls_set_*_min / nwv_bls_*_min), and the counters of the
+// calling thread's last verify call (nwv_bls_last_*)
+int set_min(nwv_ctx* ctx, std::atomic<size_t> BlsDev::*field, size_t n) {
+    BlsCtx* c;
+    int rc = ctx_of(ctx, &c);
+    if (rc) return rc;
+    for (BlsDev* d : c->devs) (d->*field).store(n, std::memory_order_relaxed);
+    return NWV_OK;
+}
+size_t get_min(const nwv_ctx* ctx, std::atomic<size_t> BlsDev::*field) {
+    BlsCtx* c;
+    if (ctx_of(const_cast<nwv_ctx*>(ctx), &c)) return 0;
+    return (c->devs[0]->*field).load(std::memory_order_relaxed);
+}
+template <size_t N>
+int last_counters(nwv_ctx* ctx, uint64_t (BlsDev::*field)[N], uint64_t* out) {
+    if (!out) return nwv_internal_set_err(NWV_ERR_ARG, "null argument");
+    BlsDev* d;
+    int rc = last_dev_of(ctx, &d);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> g(d->stat_mu);
+    for (size_t k = 0; k < N; k++) out[k] = (d->*field)[k];
+    return NWV_OK;
 }
 
 const uint8_t* dst_or_default(const uint8_t* dst, size_t* dl) {
@@ -2684,13 +2825,12 @@ __attribute__((visibility("hidden"))) void nwv_bls_ctx_release(nwv_ctx* ctx) {
 __attribute__((visibility("hidden"))) int nwv_bls_device_counters(nwv_ctx* ctx, int device_index, uint64_t* out,
                                                                   int cap) {
     BlsCtx* c;
-    int rc = ctx_of(ctx, &c);
+    BlsDev* d;
+    int rc = dev_at(ctx, device_index, &c, &d);
     if (rc) return rc;
-    if (device_index < 0 || device_index >= (int)c->devs.size())
-        return nwv_internal_set_err(NWV_ERR_ARG, "bad device index");
     const nwv::PlaceEntry e = c->place->get((size_t)device_index);
     const uint64_t v[6] = {e.ranges[NWV_ENGINE_BLS], e.items[NWV_ENGINE_BLS], e.out_ranges, e.peak,
-                           (uint64_t)c->devs[device_index]->ordinal, c->devs.size()};
+                           (uint64_t)d->ordinal, c->devs.size()};
     for (int k = 0; k < cap && k < 6; k++) out[k] = v[k];
     return 6;
 }
@@ -2702,7 +2842,7 @@ __attribute__((visibility("hidden"))) int nwv_bls_set_latency_max(nwv_ctx* ctx, 
     int rc = ctx_of(ctx, &c);
     if (rc) return rc;
     // below the shard minimum: a latency-class call is always one range
-    const size_t v = nwv::latency_clamp(n, bls_shard_min());
+    const size_t v = nwv::latency_clamp(n, bls_env().shard_min);
     for (BlsDev* d : c->devs) d->latency_max.store(v);
     return NWV_OK;
 }
@@ -2713,20 +2853,17 @@ __attribute__((visibility("hidden"))) size_t nwv_bls_latency_max(const nwv_ctx* 
 }
 __attribute__((visibility("hidden"))) int nwv_bls_diag_qos(nwv_ctx* ctx, int device_index, uint64_t out[8]) {
     BlsCtx* c;
-    int rc = ctx_of(ctx, &c);
+    BlsDev* d;
+    int rc = dev_at(ctx, device_index, &c, &d);
     if (rc) return rc;
-    if (device_index < 0 || device_index >= (int)c->devs.size())
-        return nwv_internal_set_err(NWV_ERR_ARG, "bad device index");
-    c->devs[device_index]->pool.counters(out);
+    d->pool.counters(out);
     return NWV_OK;
 }
 __attribute__((visibility("hidden"))) int nwv_bls_diag_qos_priority(nwv_ctx* ctx, int device_index, int out[3]) {
     BlsCtx* c;
-    int rc = ctx_of(ctx, &c);
+    BlsDev* d;
+    int rc = dev_at(ctx, device_index, &c, &d);
     if (rc) return rc;
-    if (device_index < 0 || device_index >= (int)c->devs.size())
-        return nwv_internal_set_err(NWV_ERR_ARG, "bad device index");
-    BlsDev* d = c->devs[device_index];
     BLS_HIP(hipSetDevice(d->ordinal));
     (void)nwv::stream_priority_range(out + 1);
     if (const BlsLane* l = d->pool.first_reserved()) BLS_HIP(hipStreamGetPriority(l->stream, &out[0]));
@@ -2769,14 +2906,15 @@ static int verify_many_impl(nwv_ctx* ctx, size_t n_keys, const uint8_t* keys, si
     if (rc) return rc;
     // items split by index over the context's devices (bls_shard.h); a small call is one range on
     // the least-loaded device, the ranges of a larger one rotate (place.h)
-    const auto ranges = bls_shard_ranges(n, c->devs.size(), bls_shard_min());
+    const auto ranges = bls_shard_ranges(n, c->devs.size(), bls_env().shard_min);
     const auto tickets = nwv::place_ranges(*c->place, ranges, NWV_ENGINE_BLS);
     t_last_dev[ctx] = tickets[0].dev();
     if (ranges.size() == 1) {
         BlsDev& d = *c->devs[tickets[0].dev()];
         // (a single range of at most nwv_latency_max items is latency class: lane_pool.h)
-        return verify_on(d, n_keys, keys, n, sigs, pk_off, pk_cnt, pk_idx, n_idx, msg_base, msg_off, msg_len, msg_bytes,
-                         dst, dst_len, status, ah.n ? &ah : nullptr, mstat.v, mstat.a, n <= d.latency_max.load());
+        const CallIn call{n_keys, keys, n, sigs, pk_off, pk_cnt, pk_idx, n_idx, msg_base, msg_off, msg_len, msg_bytes,
+                          dst, dst_len};
+        return verify_on(d, call, status, ah.n ? &ah : nullptr, mstat.v, mstat.a, n <= d.latency_max.load());
     }
     std::vector<std::string> err(ranges.size());
     std::vector<MsgStat> rstat(ranges.size());  // (the ranges run on threads of their own)
@@ -2786,9 +2924,9 @@ static int verify_many_impl(nwv_ctx* ctx, size_t n_keys, const uint8_t* keys, si
             ni = std::max<size_t>(ni, (size_t)pk_off[i] + pk_cnt[i]);
             mb = std::max<size_t>(mb, msg_off[i] + msg_len[i]);
         }
-        const int e = verify_on(*c->devs[tickets[k].dev()], n_keys, keys, hi - lo, sigs + 48 * lo, pk_off + lo,
-                                pk_cnt + lo, pk_idx, ni, msg_base, msg_off + lo, msg_len + lo, mb, dst, dst_len,
-                                status + lo, nullptr, rstat[k].v, rstat[k].a);
+        const CallIn call{n_keys, keys, hi - lo, sigs + 48 * lo, pk_off + lo, pk_cnt + lo, pk_idx, ni, msg_base,
+                          msg_off + lo, msg_len + lo, mb, dst, dst_len};
+        const int e = verify_on(*c->devs[tickets[k].dev()], call, status + lo, nullptr, rstat[k].v, rstat[k].a);
         if (e) err[k] = nwv_last_error();
         return e;
     });
@@ -2976,88 +3114,19 @@ int nwv_bls_last_path(nwv_ctx* ctx) {
     return d->last_path;
 }
 
-int nwv_bls_set_wave_batch_min(nwv_ctx* ctx, size_t n) {
-    BlsCtx* c;
-    int rc = ctx_of(ctx, &c);
-    if (rc) return rc;
-    for (BlsDev* d : c->devs) d->wave_batch_min.store(n, std::memory_order_relaxed);
-    return NWV_OK;
-}
+int nwv_bls_set_wave_batch_min(nwv_ctx* ctx, size_t n) { return set_min(ctx, &BlsDev::wave_batch_min, n); }
+size_t nwv_bls_wave_batch_min(const nwv_ctx* ctx) { return get_min(ctx, &BlsDev::wave_batch_min); }
+int nwv_bls_last_batch(nwv_ctx* ctx, uint64_t out[3]) { return last_counters(ctx, &BlsDev::last_batch, out); }
 
-size_t nwv_bls_wave_batch_min(const nwv_ctx* ctx) {
-    BlsCtx* c;
-    if (ctx_of(const_cast<nwv_ctx*>(ctx), &c)) return 0;
-    return c->devs[0]->wave_batch_min.load(std::memory_order_relaxed);
-}
+int nwv_bls_set_key_batch_min(nwv_ctx* ctx, size_t n) { return set_min(ctx, &BlsDev::key_batch_min, n); }
+size_t nwv_bls_key_batch_min(const nwv_ctx* ctx) { return get_min(ctx, &BlsDev::key_batch_min); }
+int nwv_bls_last_key_batch(nwv_ctx* ctx, uint64_t out[5]) { return last_counters(ctx, &BlsDev::last_kbatch, out); }
 
-int nwv_bls_last_batch(nwv_ctx* ctx, uint64_t out[3]) {
-    if (!out) return nwv_internal_set_err(NWV_ERR_ARG, "null argument");
-    BlsDev* d;
-    int rc = last_dev_of(ctx, &d);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> g(d->stat_mu);
-    for (int k = 0; k < 3; k++) out[k] = d->last_batch[k];
-    return NWV_OK;
-}
+int nwv_bls_set_apk_dense_min(nwv_ctx* ctx, size_t n) { return set_min(ctx, &BlsDev::apk_dense_min, n); }
+size_t nwv_bls_apk_dense_min(const nwv_ctx* ctx) { return get_min(ctx, &BlsDev::apk_dense_min); }
+int nwv_bls_last_apk_dense(nwv_ctx* ctx, uint64_t out[4]) { return last_counters(ctx, &BlsDev::last_apkd, out); }
 
-int nwv_bls_set_key_batch_min(nwv_ctx* ctx, size_t n) {
-    BlsCtx* c;
-    int rc = ctx_of(ctx, &c);
-    if (rc) return rc;
-    for (BlsDev* d : c->devs) d->key_batch_min.store(n, std::memory_order_relaxed);
-    return NWV_OK;
-}
-
-size_t nwv_bls_key_batch_min(const nwv_ctx* ctx) {
-    BlsCtx* c;
-    if (ctx_of(const_cast<nwv_ctx*>(ctx), &c)) return 0;
-    return c->devs[0]->key_batch_min.load(std::memory_order_relaxed);
-}
-
-int nwv_bls_last_key_batch(nwv_ctx* ctx, uint64_t out[5]) {
-    if (!out) return nwv_internal_set_err(NWV_ERR_ARG, "null argument");
-    BlsDev* d;
-    int rc = last_dev_of(ctx, &d);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> g(d->stat_mu);
-    for (int k = 0; k < 5; k++) out[k] = d->last_kbatch[k];
-    return NWV_OK;
-}
-
-int nwv_bls_set_apk_dense_min(nwv_ctx* ctx, size_t n) {
-    BlsCtx* c;
-    int rc = ctx_of(ctx, &c);
-    if (rc) return rc;
-    for (BlsDev* d : c->devs) d->apk_dense_min.store(n, std::memory_order_relaxed);
-    return NWV_OK;
-}
-
-size_t nwv_bls_apk_dense_min(const nwv_ctx* ctx) {
-    BlsCtx* c;
-    if (ctx_of(const_cast<nwv_ctx*>(ctx), &c)) return 0;
-    return c->devs[0]->apk_dense_min.load(std::memory_order_relaxed);
-}
-
-int nwv_bls_last_apk_dense(nwv_ctx* ctx, uint64_t out[4]) {
-    if (!out) return nwv_internal_set_err(NWV_ERR_ARG, "null argument");
-    BlsDev* d;
-    int rc = last_dev_of(ctx, &d);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> g(d->stat_mu);
-    for (int k = 0; k < 4; k++) out[k] = d->last_apkd[k];
-    return NWV_OK;
-}
-
-int nwv_bls_last_keys(nwv_ctx* ctx, uint64_t out[2]) {
-    if (!out) return nwv_internal_set_err(NWV_ERR_ARG, "null argument");
-    BlsDev* d;
-    int rc = last_dev_of(ctx, &d);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> g(d->stat_mu);
-    out[0] = d->last_keys[0];
-    out[1] = d->last_keys[1];
-    return NWV_OK;
-}
+int nwv_bls_last_keys(nwv_ctx* ctx, uint64_t out[2]) { return last_counters(ctx, &BlsDev::last_keys, out); }
 
 int nwv_bls_keycache_register(nwv_ctx* ctx, size_t n_keys, const uint8_t* keys) {
     if (n_keys && !keys) return nwv_internal_set_err(NWV_ERR_ARG, "null argument");
@@ -3129,14 +3198,7 @@ int nwv_bls_aggregate(nwv_ctx* ctx, size_t n, const uint8_t* sigs48, uint8_t out
         for (size_t j = 0; j < c->devs.size() && holder == c->devs.size(); j++) {
             BlsSigCache& sc = c->devs[j]->sc;
             std::shared_lock<std::shared_mutex> hold(sc.mu);
-            if (!sc.rec.p) continue;
-            bool all = true;
-            Sig48 k;
-            for (size_t i = 0; i < n && all; i++) {
-                std::memcpy(k.b, sigs48 + 48 * i, 48);
-                all = sc.slot.find(k) != sc.slot.end();
-            }
-            if (all) holder = j;
+            if (sc.holds_all(n, sigs48)) holder = j;
         }
     const nwv::Ticket ticket = holder < c->devs.size() ? nwv::Ticket(*c->place, holder, (uint64_t)n, NWV_ENGINE_BLS)
                                                        : nwv::Ticket(*c->place, (uint64_t)n, NWV_ENGINE_BLS);
@@ -3146,11 +3208,16 @@ int nwv_bls_aggregate(nwv_ctx* ctx, size_t n, const uint8_t* sigs48, uint8_t out
     BlsLane& L = *lane;
     // scratch: records, statuses, the sum tree's two partial-sum levels, the output, decode statuses
     const size_t n_part = (n + wave::G1SUM_N - 1) / wave::G1SUM_N + 1;  // g1_sum_per
-    const size_t w_rec = 0, w_st = al256(4 * G1_REC_WORDS * n), w_pa = al256(w_st + 4 * n),
-                 w_pb = al256(w_pa + 4 * G1P_WORDS * n_part), w_out = al256(w_pb + 4 * G1P_WORDS * n_part),
-                 w_ost = w_out + 64, w_st2 = al256(w_ost + 8), w_end = w_st2 + 4 * n;
-    if ((rc = L.in.ensure(48 * n)) || (rc = L.work.ensure(w_end)) || (rc = L.stage.ensure(128))) return rc;
-    uint8_t* w = static_cast<uint8_t*>(L.work.p);
+    Layout w;
+    const auto w_rec = w.aligned<uint32_t>(4 * G1_REC_WORDS * n);
+    const auto w_st = w.aligned<int32_t>(4 * n);
+    const auto w_pa = w.aligned<uint32_t>(4 * G1P_WORDS * n_part), w_pb = w.aligned<uint32_t>(4 * G1P_WORDS * n_part);
+    const auto w_out = w.aligned<uint8_t>(64);
+    const auto w_ost = w.packed<int32_t>(8), w_st2 = w.aligned<int32_t>(4 * n);
+    if ((rc = L.in.ensure(48 * n)) || (rc = L.work.ensure(w.end)) || (rc = L.stage.ensure(128))) return rc;
+    void* wk = L.work.p;
+    uint32_t* rec = w_rec.at(wk);
+    int32_t *st = w_st.at(wk), *sdec = w_st2.at(wk);
     // the sum of the records at `in` (through the positions idx_d when given) as a tree of
     // k_blsw_g1_sum levels; the last (one block) takes the first bad status of st_d when given
     auto sum_tree = [&](const uint32_t* in, const uint32_t* idx_d, const int32_t* st_d) {
@@ -3160,7 +3227,7 @@ int nwv_bls_aggregate(nwv_ctx* ctx, size_t n, const uint8_t* sigs48, uint8_t out
         while (m > (uint32_t)wave::G1SUM_N) {
             const uint32_t per = g1_sum_per(m);
             const uint32_t nb = (m + per - 1) / per;
-            auto* dst = reinterpret_cast<uint32_t*>(w + (flip ? w_pb : w_pa));
+            uint32_t* dst = (flip ? w_pb : w_pa).at(wk);
             hipLaunchKernelGGL(k_blsw_g1_sum, dim3(nb), dim3(64), 0, L.stream, m, src, idx_d, hom, dst, per);
             src = dst;
             idx_d = nullptr;
@@ -3169,12 +3236,12 @@ int nwv_bls_aggregate(nwv_ctx* ctx, size_t n, const uint8_t* sigs48, uint8_t out
             flip ^= 1;
         }
         hipLaunchKernelGGL(k_blsw_g1_sum_fin, dim3(1), dim3(64), 0, L.stream, m, src, idx_d, hom,
-                           st_d ? (uint32_t)n : 0u, st_d, w + w_out, reinterpret_cast<int32_t*>(w + w_ost));
+                           st_d ? (uint32_t)n : 0u, st_d, w_out.at(wk), w_ost.at(wk));
     };
     auto fetch = [&]() -> int {
         BLS_HIP(hipGetLastError());
         uint8_t* hs = static_cast<uint8_t*>(L.stage.p);
-        BLS_HIP(hipMemcpyAsync(hs, w + w_out, 64 + 8, hipMemcpyDeviceToHost, L.stream));
+        BLS_HIP(hipMemcpyAsync(hs, w_out.at(wk), 64 + 8, hipMemcpyDeviceToHost, L.stream));
         BLS_HIP(hipStreamSynchronize(L.stream));
         int32_t st;
         std::memcpy(&st, hs + 64, 4);
@@ -3186,39 +3253,23 @@ int nwv_bls_aggregate(nwv_ctx* ctx, size_t n, const uint8_t* sigs48, uint8_t out
     // every signature verified by an earlier call: sum the ring's records (no decode, no G1 check)
     if (!(d->flags & NWV_FLAG_NO_SIGCACHE)) {
         std::shared_lock<std::shared_mutex> hold(d->sc.mu);
-        if (d->sc.rec.p && n <= SC_CAP) {
-            std::vector<uint32_t> pos(n);
-            bool all = true;
-            Sig48 k;
-            for (size_t i = 0; i < n && all; i++) {
-                std::memcpy(k.b, sigs48 + 48 * i, 48);
-                auto it = d->sc.slot.find(k);
-                if (it == d->sc.slot.end()) all = false;
-                else pos[i] = it->second;
-            }
-            if (all) {
-                BLS_HIP(nwv_stage::stage_h2d(L.in.p, pos.data(), 4 * n, L.stream));
-                sum_tree(static_cast<const uint32_t*>(d->sc.rec.p), static_cast<const uint32_t*>(L.in.p), nullptr);
-                return fetch();
-            }
+        std::vector<uint32_t> pos(n <= SC_CAP ? n : 0);
+        if (d->sc.holds_all(n, sigs48, pos.data())) {
+            BLS_HIP(nwv_stage::stage_h2d(L.in.p, pos.data(), 4 * n, L.stream));
+            sum_tree(static_cast<const uint32_t*>(d->sc.rec.p), static_cast<const uint32_t*>(L.in.p), nullptr);
+            return fetch();
         }
     }
     BLS_HIP(nwv_stage::stage_h2d(L.in.p, sigs48, 48 * n, L.stream));
+    const uint8_t* sig_d = static_cast<const uint8_t*>(L.in.p);
     if (n <= 1024) {  // decode on one lane each, the G1 checks on a wave each
-        auto* sdec = reinterpret_cast<int32_t*>(w + w_st2);
-        hipLaunchKernelGGL(k_blsw_sigdec, dim3(kBlocks(n)), dim3(BLS_LANES), 0, L.stream, (uint32_t)n,
-                           (const uint8_t*)L.in.p, reinterpret_cast<uint32_t*>(w + w_rec), sdec);
-        hipLaunchKernelGGL(k_blsw_sub, dim3((unsigned)n), dim3(64), 0, L.stream, (uint32_t)n,
-                           reinterpret_cast<const uint32_t*>(w + w_rec), (const int32_t*)sdec,
-                           reinterpret_cast<int32_t*>(w + w_st));
-        hipLaunchKernelGGL(k_bls_st_join, dim3(kBlocks(n)), dim3(BLS_LANES), 0, L.stream, (uint32_t)n,
-                           (const int32_t*)sdec, reinterpret_cast<int32_t*>(w + w_st));
+        hipLaunchKernelGGL(k_blsw_sigdec, dim3(kBlocks(n)), dim3(BLS_LANES), 0, L.stream, (uint32_t)n, sig_d, rec, sdec);
+        hipLaunchKernelGGL(k_blsw_sub, dim3((unsigned)n), dim3(64), 0, L.stream, (uint32_t)n, rec, sdec, st);
+        hipLaunchKernelGGL(k_bls_st_join, dim3(kBlocks(n)), dim3(BLS_LANES), 0, L.stream, (uint32_t)n, sdec, st);
     } else {
-        hipLaunchKernelGGL(k_bls_sigs, dim3(kBlocks(n)), dim3(BLS_LANES), 0, L.stream, (uint32_t)n,
-                           (const uint8_t*)L.in.p, reinterpret_cast<uint32_t*>(w + w_rec),
-                           reinterpret_cast<int32_t*>(w + w_st));
+        hipLaunchKernelGGL(k_bls_sigs, dim3(kBlocks(n)), dim3(BLS_LANES), 0, L.stream, (uint32_t)n, sig_d, rec, st);
     }
-    sum_tree(reinterpret_cast<const uint32_t*>(w + w_rec), nullptr, reinterpret_cast<const int32_t*>(w + w_st));
+    sum_tree(rec, nullptr, st);
     return fetch();
 }
 

@@ -83,6 +83,21 @@ def sc_forgery(bls, layout):
     return rig.run(items)
 
 
+def sc_two_rejected(bls, layout):
+    """23 items at group size 5, two forgeries a run: in groups 0 and 3 (the accepted groups 1 and 2
+    between them share the re-check launch), then in group 0 and the partial last group"""
+    rig = Rig(bls, layout, 77)
+    valid = rig.valid(23)
+    runs = {}
+    for name, bad in (("apart", (2, 17)), ("to_the_end", (2, 21))):
+        items = list(valid)
+        for k in bad:
+            s, ks, m = items[k]
+            items[k] = (s, ks, m[:-1] + bytes([m[-1] ^ 1]))
+        runs[name] = rig.run(items)
+    return {"runs": runs}
+
+
 def sc_cancel(bls, layout):
     rig = Rig(bls, layout, 73)
     items = rig.valid(16)

@@ -31,9 +31,9 @@ void bkb_get(void* h, int which, uint32_t* out) {
     if (which < 0 || which > 7 || v[which]->empty()) return;
     std::memcpy(out, v[which]->data(), 4 * v[which]->size());
 }
-// the ranges of key_batch_ranges as lo, hi pairs into out (room for 2 n words); returns their number
+// the ranges of recheck_ranges as lo, hi pairs into out (room for 2 n words); returns their number
 uint64_t bkb_ranges(uint64_t n, const uint8_t* need, uint64_t gap, uint64_t* out) {
-    const auto r = nwv::key_batch_ranges((size_t)n, need, (size_t)gap);
+    const auto r = nwv::recheck_ranges((size_t)n, need, (size_t)gap);
     for (size_t k = 0; k < r.size(); k++) {
         out[2 * k] = r[k].first;
         out[2 * k + 1] = r[k].second;

@@ -151,14 +151,56 @@ def test_half_rule(lib):
     assert p["run"] == 1 and p["n_eligible"] == 4 and p["items"] == [0, 1, 2, 3] and p["outside"] == [4, 5, 6, 7]
 
 
+def ranges(lib, need, gap):
+    n = len(need)
+    a = np.array(need + [0], dtype=u8)
+    out = np.zeros(2 * n + 2, dtype=u64)
+    k = int(lib.bkb_ranges(n, a.ctypes.data, gap, out.ctypes.data))
+    return [(int(out[2 * j]), int(out[2 * j + 1])) for j in range(k)]
+
+
+def group_loop_ranges(n, grp, gok, gap):
+    """the wave batch check's re-check loop over its groups' verdicts, as the engine ran it before
+    recheck_ranges served both checks: (lo, hi) per launch, and the rejected groups counted"""
+    ng = (n + grp - 1) // grp
+    out, rejected, g = [], 0, 0
+    while g < ng:
+        if gok[g] == 1:
+            g += 1
+            continue
+        e = g + 1  # the range's end: past its last rejected group
+        rejected += 1
+        q = e
+        while q < ng and (q - e) * grp < gap:
+            if gok[q] != 1:
+                e = q + 1
+                rejected += 1
+            q += 1
+        out.append((g * grp, min(n, e * grp)))
+        g = e
+    return out, rejected
+
+
 def test_ranges_share_launches_below_the_gap(lib):
-    rnd = random.Random(5)
+    rnd, grnd = random.Random(5), random.Random(6)
+    # group-shaped flags (every item of a rejected group marked, the last group partial): the ranges
+    # of the wave batch check's former loop over the groups
+    for grp in (1, 5, 7):
+        for gap in (1, grp, 3 * grp, 1024):
+            for n in (grp * 9 + 1 if grp > 1 else 10, grp * 40 + grp // 2 + 1, 2311):
+                if grp > 1 and n % grp == 0:
+                    n += 1
+                ng = (n + grp - 1) // grp
+                for p in (0.0, 0.1, 0.5, 1.0):
+                    gok = [0 if grnd.random() < p else 1 for _ in range(ng)]
+                    need = [int(gok[i // grp] != 1) for i in range(n)]
+                    want, rejected = group_loop_ranges(n, grp, gok, gap)
+                    assert ranges(lib, need, gap) == want, (grp, gap, n, gok)
+                    assert rejected == sum(1 for v in gok if v != 1)
+                    assert all(hi <= n for _, hi in want)
     for n, gap in [(1, 4), (40, 1), (200, 16), (5000, 1024)]:
         need = [int(rnd.random() < 0.03) for _ in range(n)]
-        a = np.array(need + [0], dtype=u8)
-        out = np.zeros(2 * n + 2, dtype=u64)
-        k = int(lib.bkb_ranges(n, a.ctypes.data, gap, out.ctypes.data))
-        got = [(int(out[2 * j]), int(out[2 * j + 1])) for j in range(k)]
+        got = ranges(lib, need, gap)
         want = []
         for i in range(n):
             if need[i]:

@@ -27,7 +27,7 @@ SCENARIOS = ["default_off", "noted_filled_hit", "held_set", "gate", "identity", 
 
 def _child(names, **env):
     e = dict(os.environ, NWV_BLS_DEVICE_REPLICAS="1")
-    for k in ("NWV_BLS_WAVE_MAX", "NWV_DEVICE_REPLICAS", "NWV_BLS_SUB_FLAT"):
+    for k in ("NWV_BLS_WAVE_MAX", "NWV_DEVICE_REPLICAS"):
         e.pop(k, None)
     e.update(env)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "bls_apk_ring_gpu_check.py")] + list(names),

@@ -25,7 +25,7 @@ def cnt(**kw):
 
 def _child(scenario, arg="", **env):
     e = dict(os.environ, NWV_BLS_DEVICE_REPLICAS="1")
-    for k in ("NWV_BLS_WAVE_MAX", "NWV_DEVICE_REPLICAS", "NWV_BLS_SUB_FLAT"):
+    for k in ("NWV_BLS_WAVE_MAX", "NWV_DEVICE_REPLICAS"):
         e.pop(k, None)
     e.update(env)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "bls_msg_ring_gpu_check.py"), scenario, arg],

@@ -55,6 +55,20 @@ def test_one_forgery_rechecks_one_group(layout, pack):
     assert out["batch"] == [5, 1, 5]
 
 
+def test_two_rejected_groups_share_one_recheck_range():
+    """forgeries in items 2 and 17 reject groups 0 and 3: one re-check launch over items 0..19, the
+    accepted groups 1 and 2 included; in items 2 and 21 they reject group 0 and the partial last
+    group, and the launch ends at the call's 23 items, not at the group's 25"""
+    out = _child("two_rejected", "registered", "3")["runs"]
+    for name, bad, batch in (("apart", [2, 17], [5, 2, 20]), ("to_the_end", [2, 21], [5, 2, 23])):
+        run = out[name]
+        assert [i for i, w in enumerate(run["want"]) if w] == bad
+        assert all(run["want"][i] == VERIFY_FAIL for i in bad)
+        assert run["got"] == run["want"], (name, run)
+        assert run["path"] == "wave_batch_rejected_then_per_item", (name, run)
+        assert run["batch"] == batch, (name, run)
+
+
 @pytest.mark.parametrize("layout", LAYOUTS)
 def test_cancelling_forgeries_in_one_group(layout):
     """sig_a + D and sig_b - D in one group: the product of the two items' equations without
