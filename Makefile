@@ -12,7 +12,7 @@ BLS_SRC := narwhal_amd/csrc/nwv_bls.hip narwhal_amd/csrc/bls381.h narwhal_amd/cs
 # headers that both engines' translation units include (they stay in CSRC)
 BLS_SHARED := narwhal_amd/csrc/shard.h narwhal_amd/csrc/place.h narwhal_amd/csrc/lane_pool.h narwhal_amd/csrc/lane_stream.h
 CSRC := $(filter-out $(BLS_SRC),$(wildcard narwhal_amd/csrc/*.h narwhal_amd/csrc/*.hip narwhal_amd/csrc/*.cpp)) \
-	include/nwv.h include/nwv_types.h include/nwv_service.h
+	include/nwv.h include/nwv_types.h include/nwv_service.h include/nwv_digest_stream.h
 
 all: lib oracle hostemu tools
 
@@ -48,7 +48,13 @@ hostemu: tests/_build/libhostemu.so tests/_build/libsvcstub.so tests/_build/libb
 	tests/_build/libblsapkring.so tests/_build/libblsaremu.so tests/_build/libblskeybatch.so \
 	tests/_build/libblskbemu.so tests/_build/libblsademu.so tests/_build/libblswvemu.so \
 	tests/_build/libcombpassemu.so \
-	tests/_build/libtailrcemu.so tests/_build/liblanepool.so
+	tests/_build/libtailrcemu.so tests/_build/liblanepool.so tests/_build/libdstream.so
+# the digest stream (digest_stream.h: chunk pool, hold-back rule, tick plan, pump, callbacks) over a stub
+# device that runs the work records with blake2b.h's compression (tests/test_digest_stream_host.py)
+tests/_build/libdstream.so: tests/hostemu/digest_stream_stub.cpp narwhal_amd/csrc/digest_stream.h \
+		narwhal_amd/csrc/blake2b.h narwhal_amd/csrc/sha512.h narwhal_amd/csrc/fe25519.h
+	@mkdir -p tests/_build
+	$(HIPCC) -std=c++17 -O1 -g --offload-host-only -x hip -fPIC -shared -pthread -o $@ tests/hostemu/digest_stream_stub.cpp
 # the wave interpreter one program at a time with its limb bounds evaluated (BLS_BOUNDS_CHECK;
 # tests/test_bls_wave_vectors_hostemu.py)
 tests/_build/libblswvemu.so: tests/hostemu/bls_wave_vectors_hostemu.cpp $(BLS_SRC) $(BLS_SHARED)

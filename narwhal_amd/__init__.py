@@ -5,5 +5,6 @@ SURVEY.md §8).  The product is the C-ABI library narwhal_amd/lib/lib
 (include/nwv.h); this package only binds it.
 """
 from ._lib import Engine, NwvError, load  # noqa: F401
+from .digest_stream import DigestStream  # noqa: F401
 
-__all__ = ["Engine", "NwvError", "load"]
+__all__ = ["Engine", "NwvError", "load", "DigestStream"]

@@ -137,6 +137,18 @@ def load():
         "nwv_bls_set_apk_dense_min": ([_vp, _sz], _i32),
         "nwv_bls_apk_dense_min": ([_vp], _sz),
         "nwv_bls_last_apk_dense": ([_vp, _vp], _i32),
+        # the digest stream (narwhal_amd.digest_stream.DigestStream): ctx, stream id, ...; a message's
+        # bytes as a bytes object, its callback as a function pointer, its user word as an integer
+        "nwv_dstream_open": ([_vp, _i32, _sz, _sz, _sz], _i32),
+        "nwv_dstream_submit": ([_vp, _i32, ctypes.c_char_p, _sz, _vp, _vp, _vp], _i32),
+        "nwv_dstream_submit_serialized": ([_vp, _i32, ctypes.c_char_p, _sz, _vp, ctypes.POINTER(ctypes.c_int64),
+                                           _vp, _vp], _i32),
+        "nwv_dstream_begin": ([_vp, _i32, _vp, _vp, _vp, ctypes.POINTER(ctypes.c_uint64)], _i32),
+        "nwv_dstream_update": ([_vp, _i32, ctypes.c_uint64, ctypes.c_char_p, _sz], _i32),
+        "nwv_dstream_finish": ([_vp, _i32, ctypes.c_uint64], _i32),
+        "nwv_dstream_flush": ([_vp, _i32], _i32),
+        "nwv_dstream_stats": ([_vp, _i32, _vp], _i32),
+        "nwv_dstream_close": ([_vp, _i32], _i32),
     }
     for name, (args, res) in newer.items():
         f = getattr(lib, name, None)

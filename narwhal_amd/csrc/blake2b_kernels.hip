@@ -276,3 +276,118 @@ extern "C" __global__ void __launch_bounds__(256) k_batch_compact(
         payload_len[i] = err_off >= 0 ? 0 : walk_dst;
     }
 }
+
+// ---- resumable slices of long messages (the digest stream, digest_stream.h) ----------------------
+// The quad form of k_blake2b_quad, one work record (nwv::DsRecord, 8 dwords) a quad: run `nblocks`
+// compressions from block `first_block` of pool chunk `chunk` on the chaining value of message slot
+// `slot`.  state holds 16 words a slot (h[8], the byte counter t, 7 unused); a record flagged
+// DS_FIRST starts from the IV and parameter block instead of loading, every record stores the state
+// back, and one flagged DS_LAST compresses its final block with t += last_len (0..128) and the
+// finalisation flag, then stores the digest at 32 * slot of out and out2 (coherent pinned host
+// memory).  Chunks are 128-byte aligned and zero-padded by the host, so lane q loads its 32 bytes
+// of a block with two aligned 16-byte loads, one block ahead, and nothing is trimmed.
+// Fail closed: a slot >= n_slots is dropped, chunk is clamped to the pool, first_block and
+// nblocks to the slice, last_len to 128: no record loops longer than slice_blocks compressions or
+// reads outside the pool.  No waits, no atomics; a launch is at most slice_blocks compressions long.
+namespace {
+// one compression of the quad's message on block words m[16] (LDS); tb = t after this block
+__device__ __forceinline__ void b2_quad_compress(uint64_t& h0, uint64_t& h1, const uint64_t* m, uint64_t iv0,
+                                                 uint64_t iv1, int q, uint64_t tb, bool last, bool live) {
+    const int sh = 4 * q;
+    uint64_t mw[12][4];
+#pragma unroll
+    for (int r = 0; r < 12; r++) {
+        mw[r][0] = m[(sigma_pack(r, 0) >> sh) & 15];
+        mw[r][1] = m[(sigma_pack(r, 1) >> sh) & 15];
+        mw[r][2] = m[(sigma_pack(r, 8) >> sh) & 15];
+        mw[r][3] = m[(sigma_pack(r, 9) >> sh) & 15];
+    }
+    uint64_t va = h0, vb = h1, vc = iv0, vd = iv1;
+    if (q == 0) vd ^= tb;
+    if (q == 2 && last) vd = ~vd;
+#pragma unroll
+    for (int r = 0; r < 12; r++) {
+        b2_g(va, vb, vc, vd, mw[r][0], mw[r][1]);
+        vb = quad_rot<QP_NEXT1>(vb);
+        vc = quad_rot<QP_NEXT2>(vc);
+        vd = quad_rot<QP_NEXT3>(vd);
+        b2_g(va, vb, vc, vd, mw[r][2], mw[r][3]);
+        vb = quad_rot<QP_NEXT3>(vb);
+        vc = quad_rot<QP_NEXT2>(vc);
+        vd = quad_rot<QP_NEXT1>(vd);
+    }
+    if (live) {
+        h0 ^= va ^ vc;
+        h1 ^= vb ^ vd;
+    }
+}
+}  // namespace
+
+extern "C" __global__ void __launch_bounds__(64) k_blake2b_slice(
+    uint32_t nrec, const uint4* __restrict__ recs, const uint8_t* __restrict__ pool, uint32_t slice_blocks,
+    uint32_t pool_chunks, uint32_t n_slots, uint64_t* __restrict__ state, uint32_t* __restrict__ out,
+    uint32_t* __restrict__ out2) {
+    __shared__ uint64_t blk[16][16];
+    const int lane = threadIdx.x, q = lane & 3, sl = lane >> 2;
+    const uint32_t i = blockIdx.x * 16 + sl;
+    uint4 ra = make_uint4(0, 0, 0, 0), rb = ra;  // slot, chunk, first_block, nblocks | flags, last_len
+    if (i < nrec) {
+        ra = recs[2 * (size_t)i];
+        rb = recs[2 * (size_t)i + 1];
+    }
+    const bool active = i < nrec && ra.x < n_slots && pool_chunks > 0;
+    const uint32_t slot = active ? ra.x : 0;
+    const uint32_t chunk = active ? (ra.y < pool_chunks ? ra.y : pool_chunks - 1) : 0;
+    const uint32_t fb = ra.z < slice_blocks ? ra.z : slice_blocks;
+    const uint32_t nb = active ? (ra.w < slice_blocks - fb ? ra.w : slice_blocks - fb) : 0;
+    const bool first = (rb.x & 1u) != 0, fin = (rb.x & 2u) != 0;
+    const uint32_t last_len = rb.y < 128u ? rb.y : 128u;
+    uint32_t nmax = nb;  // blocks of the longest record of the wave
+    for (int o = 4; o < 64; o <<= 1) {
+        const uint32_t t = __shfl_xor(nmax, o);
+        nmax = t > nmax ? t : nmax;
+    }
+    const uint64_t iv0 = iv64(q), iv1 = iv64(q + 4);
+    uint64_t* st = state + 16 * (size_t)slot;
+    uint64_t h0 = iv0, h1 = iv1, t = 0;
+    if (q == 0) h0 ^= 0x01010000u ^ 32u;
+    if (active && !first) {
+        h0 = st[q];
+        h1 = st[4 + q];
+        t = st[8];
+    }
+    const uint4* p = reinterpret_cast<const uint4*>(pool + ((size_t)chunk * slice_blocks + fb) * 128 + 32 * q);
+    uint4 w0 = make_uint4(0, 0, 0, 0), w1 = w0;
+    if (nb > 0) {
+        w0 = p[0];
+        w1 = p[1];
+    }
+#pragma unroll 1
+    for (uint32_t b = 0; b < nmax; b++) {
+        const bool live = b < nb;
+        blk[sl][4 * q + 0] = (uint64_t)w0.x | ((uint64_t)w0.y << 32);
+        blk[sl][4 * q + 1] = (uint64_t)w0.z | ((uint64_t)w0.w << 32);
+        blk[sl][4 * q + 2] = (uint64_t)w1.x | ((uint64_t)w1.y << 32);
+        blk[sl][4 * q + 3] = (uint64_t)w1.z | ((uint64_t)w1.w << 32);
+        if (b + 1 < nb) {
+            w0 = p[8 * (size_t)(b + 1)];
+            w1 = p[8 * (size_t)(b + 1) + 1];
+        }
+        __syncthreads();
+        const bool last = fin && b + 1 == nb;
+        if (live) t += last ? last_len : 128u;
+        b2_quad_compress(h0, h1, blk[sl], iv0, iv1, q, t, last, live);
+        __syncthreads();
+    }
+    if (active) {
+        st[q] = h0;
+        st[4 + q] = h1;
+        if (q == 0) st[8] = t;
+        if (fin) {
+            out[8 * (size_t)slot + 2 * q] = (uint32_t)h0;
+            out[8 * (size_t)slot + 2 * q + 1] = (uint32_t)(h0 >> 32);
+            out2[8 * (size_t)slot + 2 * q] = (uint32_t)h0;
+            out2[8 * (size_t)slot + 2 * q + 1] = (uint32_t)(h0 >> 32);
+        }
+    }
+}

@@ -21,12 +21,14 @@
 #include <vector>
 
 #include "../../include/nwv.h"
+#include "../../include/nwv_digest_stream.h"
 #include "blake2b_kernels.hip"
 #include "ed25519_kernels.hip"
 #include "msm_kernels.hip"
 #include "tiny_kernels.hip"
 #include "comb_kernels.hip"
 #include "each_kernels.hip"
+#include "digest_stream.h"
 #include "group_keys.h"
 #include "keycache_alloc.h"
 #include "lane_pool.h"
@@ -1461,6 +1463,8 @@ bool verdicts_all_valid(const uint64_t* bits, size_t n) {
 #define NWV_COMB_PASS_L_DEFAULT 16
 #endif
 
+struct DStreamDev;  // a digest stream on its device (below, with the nwv_dstream_* entry points)
+
 struct nwv_ctx {
     std::vector<Gpu*> devs;
     std::vector<int> ordinals;  // the HIP devices the context was opened over (devs counts replicas too)
@@ -1488,7 +1492,13 @@ struct nwv_ctx {
     // nwv_ed25519_verify_batch_grouped (the trait surface): calls, and how each one ran -- every
     // key from the cache, keyed and uncached, un-keyed (nwv_diag_grouped)
     std::atomic<uint64_t> n_grouped[4] = {};
+    // the open digest streams (nwv_dstream_open; the id is the index), guarded by ds_mu
+    static constexpr int MAX_DSTREAMS = 8;
+    std::mutex ds_mu;
+    std::shared_ptr<DStreamDev> ds[MAX_DSTREAMS];
 };
+// closes every open digest stream of the context (nwv_free, before the devices go)
+static void ds_close_all(nwv_ctx* ctx);
 
 // Per-kernel device time of the staged pipelines (HIP events on the batch's own stream).
 struct KernelLog {
@@ -1638,6 +1648,7 @@ int nwv_init_device(nwv_ctx** out, int device_ordinal, uint32_t flags) {
 
 void nwv_free(nwv_ctx* ctx) {
     if (!ctx) return;
+    ds_close_all(ctx);
     nwv_bls_ctx_release(ctx);  // the BLS12-381 engine's per-context state (nwv_bls.hip)
     for (Gpu* d : ctx->devs) {
         gpu_close(*d);
@@ -3203,6 +3214,203 @@ int nwv_ed25519_sign_many(nwv_ctx* ctx, size_t n, const uint8_t* seeds, const ui
         NWV_HIP(hipStreamSynchronize(d.stream));
         return NWV_OK;
     });
+}
+
+}  // extern "C"
+
+// ---- the digest stream (include/nwv_digest_stream.h) --------------------------------------------
+// The stream itself -- chunk pool, hold-back rule, tick plan, pump thread, callbacks -- is
+// digest_stream.h (host code, tests/test_digest_stream_host.py).  Here is its device: a pinned host
+// pool and a device pool of the same chunks, a copy stream and a compute stream of normal priority
+// (the latency class's reserved lanes still go first), and k_blake2b_slice.  A tick's uploads and
+// its records go on the copy stream; the kernel waits for them through an event on the compute
+// stream, so the copy of tick n + 1 runs under the kernel of tick n.  No lane is leased.  While the
+// stream has messages in flight it holds one range on its device in the context's load table.
+static_assert(nwv::DS_OK == NWV_OK && nwv::DS_ERR_ARG == NWV_ERR_ARG && nwv::DS_ERR_REENTRANT == NWV_ERR_REENTRANT,
+              "digest_stream.h's result codes");
+
+struct DStreamDev final : nwv::DsBackend {
+    int ordinal = -1;
+    size_t dev_index = 0, slice = 0, chunks = 0, messages = 0;
+    std::shared_ptr<nwv::PlaceTable> place;
+    nwv::Ticket load;
+    void* hpool = nullptr;        // pinned
+    void* hdig = nullptr;         // coherent pinned: the kernel stores the digests here too
+    void* hrecs[2] = {nullptr, nullptr};  // pinned: a tick's records
+    DevBuf dpool, drecs[2], dstate, dout;
+    hipStream_t copy_s = nullptr, comp_s = nullptr;
+    hipEvent_t copied[2] = {nullptr, nullptr}, ran[2] = {nullptr, nullptr};
+    std::unique_ptr<nwv::DigestStream> core;  // (destroyed first: its pump uses everything above)
+
+    int open() {
+        NWV_HIP(hipSetDevice(ordinal));
+        const size_t pool_bytes = chunks * slice * nwv::DS_BLOCK, rec_bytes = messages * sizeof(nwv::DsRecord);
+        NWV_HIP(hipHostMalloc(&hpool, pool_bytes, hipHostMallocDefault));
+        NWV_HIP(hipHostMalloc(&hdig, 32 * messages, hipHostMallocCoherent | hipHostMallocMapped));
+        int rc;
+        for (int b = 0; b < 2; b++) {
+            NWV_HIP(hipHostMalloc(&hrecs[b], rec_bytes, hipHostMallocDefault));
+            if ((rc = drecs[b].ensure(rec_bytes))) return rc;
+            NWV_HIP(hipEventCreateWithFlags(&copied[b], hipEventDisableTiming));
+            NWV_HIP(hipEventCreateWithFlags(&ran[b], hipEventDisableTiming));
+        }
+        if ((rc = dpool.ensure(pool_bytes)) || (rc = dstate.ensure(128 * messages)) || (rc = dout.ensure(32 * messages)))
+            return rc;
+        NWV_HIP(hipStreamCreateWithFlags(&copy_s, hipStreamNonBlocking));
+        NWV_HIP(hipStreamCreateWithFlags(&comp_s, hipStreamNonBlocking));
+        core.reset(new nwv::DigestStream(*this, slice, chunks, messages));
+        return NWV_OK;
+    }
+    ~DStreamDev() override {
+        core.reset();  // completes what is finished, stops the pump
+        (void)hipSetDevice(ordinal);
+        if (comp_s) (void)hipStreamSynchronize(comp_s);
+        if (copy_s) (void)hipStreamSynchronize(copy_s);
+        for (int b = 0; b < 2; b++) {
+            if (copied[b]) (void)hipEventDestroy(copied[b]);
+            if (ran[b]) (void)hipEventDestroy(ran[b]);
+            if (hrecs[b]) (void)hipHostFree(hrecs[b]);
+            drecs[b].release();
+        }
+        if (comp_s) (void)hipStreamDestroy(comp_s);
+        if (copy_s) (void)hipStreamDestroy(copy_s);
+        dpool.release();
+        dstate.release();
+        dout.release();
+        if (hpool) (void)hipHostFree(hpool);
+        if (hdig) (void)hipHostFree(hdig);
+    }
+
+    uint8_t* host_pool() override { return static_cast<uint8_t*>(hpool); }
+    const uint8_t* digests() override { return static_cast<const uint8_t*>(hdig); }
+    int submit(int b, const nwv::DsTick& t) override {
+        NWV_HIP(hipSetDevice(ordinal));
+        const size_t n = t.recs.size();
+        if (n > messages) return set_err(NWV_ERR_ARG, "digest stream: more records than message slots");
+        const size_t pool_bytes = chunks * slice * nwv::DS_BLOCK;
+        for (const nwv::DsCopy& c : t.copies) {
+            if (c.off > pool_bytes || c.len > pool_bytes - c.off)
+                return set_err(NWV_ERR_ARG, "digest stream: copy range outside the pool");
+            NWV_HIP(hipMemcpyAsync(dpool.as<uint8_t>() + c.off, host_pool() + c.off, (size_t)c.len,
+                                   hipMemcpyHostToDevice, copy_s));
+        }
+        std::memcpy(hrecs[b], t.recs.data(), n * sizeof(nwv::DsRecord));
+        NWV_HIP(hipMemcpyAsync(drecs[b].p, hrecs[b], n * sizeof(nwv::DsRecord), hipMemcpyHostToDevice, copy_s));
+        NWV_HIP(hipEventRecord(copied[b], copy_s));
+        NWV_HIP(hipStreamWaitEvent(comp_s, copied[b], 0));
+        hipLaunchKernelGGL(k_blake2b_slice, dim3((unsigned)((n + 15) / 16)), dim3(64), 0, comp_s, (uint32_t)n,
+                           drecs[b].as<uint4>(), dpool.as<uint8_t>(), (uint32_t)slice, (uint32_t)chunks,
+                           (uint32_t)messages, dstate.as<uint64_t>(), dout.as<uint32_t>(), static_cast<uint32_t*>(hdig));
+        NWV_HIP(hipGetLastError());
+        NWV_HIP(hipEventRecord(ran[b], comp_s));
+        return NWV_OK;
+    }
+    int wait(int b) override {
+        NWV_HIP(hipEventSynchronize(ran[b]));
+        return NWV_OK;
+    }
+    void busy(bool on) override {
+        if (on)
+            load = nwv::Ticket(*place, dev_index, 1, 0);
+        else
+            load.release();
+    }
+};
+
+static std::shared_ptr<DStreamDev> ds_get(nwv_ctx* ctx, int ds) {
+    if (!ctx || ds < 0 || ds >= nwv_ctx::MAX_DSTREAMS) return nullptr;
+    std::lock_guard<std::mutex> g(ctx->ds_mu);
+    return ctx->ds[ds];
+}
+// the stream leaves the context's table: its id is free again
+static std::shared_ptr<DStreamDev> ds_take(nwv_ctx* ctx, int ds) {
+    if (!ctx || ds < 0 || ds >= nwv_ctx::MAX_DSTREAMS) return nullptr;
+    std::lock_guard<std::mutex> g(ctx->ds_mu);
+    std::shared_ptr<DStreamDev> s = std::move(ctx->ds[ds]);
+    ctx->ds[ds].reset();
+    return s;
+}
+static void ds_close_all(nwv_ctx* ctx) {
+    for (int k = 0; k < nwv_ctx::MAX_DSTREAMS; k++)
+        if (const auto s = ds_take(ctx, k)) (void)s->core->close();
+}
+// the planner's result codes are the library's; its failures carry no message of their own
+static int ds_rc(int rc, const char* what) { return rc == NWV_OK ? rc : set_err(rc, what); }
+
+extern "C" {
+
+int nwv_dstream_open(nwv_ctx* ctx, int device_index, size_t slice_blocks, size_t pool_chunks, size_t max_messages) {
+    if (!ctx || device_index < -1 || device_index >= (int)ctx->devs.size())
+        return set_err(NWV_ERR_ARG, "bad context or device index");
+    const size_t slice = slice_blocks ? slice_blocks : nwv::DigestStream::default_slice();
+    const size_t msgs = max_messages ? max_messages : nwv::DigestStream::default_messages();
+    const size_t chunks = pool_chunks ? pool_chunks : nwv::DigestStream::default_chunks(slice, msgs);
+    if (!nwv::DigestStream::config_ok(slice, chunks, msgs))
+        return set_err(NWV_ERR_ARG, "digest stream: pool_chunks must be at least 2 max_messages");
+    auto dev = std::make_shared<DStreamDev>();
+    // -1: the least-loaded device now (the ticket is only the look; the stream counts while it is busy)
+    dev->dev_index = device_index >= 0 ? (size_t)device_index : nwv::Ticket(*ctx->place, 0).dev();
+    dev->ordinal = ctx->devs[dev->dev_index]->ordinal;
+    dev->place = ctx->place;
+    dev->slice = slice;
+    dev->chunks = chunks;
+    dev->messages = msgs;
+    const int rc = dev->open();
+    if (rc) return rc;
+    std::lock_guard<std::mutex> g(ctx->ds_mu);
+    for (int k = 0; k < nwv_ctx::MAX_DSTREAMS; k++)
+        if (!ctx->ds[k]) {
+            ctx->ds[k] = std::move(dev);
+            return k;
+        }
+    return set_err(NWV_ERR_ARG, "too many digest streams");
+}
+
+int nwv_dstream_submit(nwv_ctx* ctx, int ds, const uint8_t* data, size_t len, uint8_t* digest_out, nwv_done_fn done,
+                       void* user) {
+    const auto s = ds_get(ctx, ds);
+    if (!s) return set_err(NWV_ERR_ARG, "no such digest stream");
+    return ds_rc(s->core->submit(data, len, digest_out, done, user), "nwv_dstream_submit");
+}
+int nwv_dstream_submit_serialized(nwv_ctx* ctx, int ds, const uint8_t* buf, size_t len, uint8_t* digest_out,
+                                  int64_t* err_offset_out, nwv_done_fn done, void* user) {
+    const auto s = ds_get(ctx, ds);
+    if (!s) return set_err(NWV_ERR_ARG, "no such digest stream");
+    return ds_rc(s->core->submit_serialized(buf, len, digest_out, err_offset_out, done, user),
+                 "nwv_dstream_submit_serialized");
+}
+int nwv_dstream_begin(nwv_ctx* ctx, int ds, uint8_t* digest_out, nwv_done_fn done, void* user, uint64_t* msg_id) {
+    const auto s = ds_get(ctx, ds);
+    if (!s) return set_err(NWV_ERR_ARG, "no such digest stream");
+    return ds_rc(s->core->begin(digest_out, done, user, msg_id), "nwv_dstream_begin");
+}
+int nwv_dstream_update(nwv_ctx* ctx, int ds, uint64_t msg_id, const uint8_t* data, size_t len) {
+    const auto s = ds_get(ctx, ds);
+    if (!s) return set_err(NWV_ERR_ARG, "no such digest stream");
+    return ds_rc(s->core->update(msg_id, data, len), "nwv_dstream_update");
+}
+int nwv_dstream_finish(nwv_ctx* ctx, int ds, uint64_t msg_id) {
+    const auto s = ds_get(ctx, ds);
+    if (!s) return set_err(NWV_ERR_ARG, "no such digest stream");
+    return ds_rc(s->core->finish(msg_id), "nwv_dstream_finish");
+}
+int nwv_dstream_flush(nwv_ctx* ctx, int ds) {
+    const auto s = ds_get(ctx, ds);
+    if (!s) return set_err(NWV_ERR_ARG, "no such digest stream");
+    return ds_rc(s->core->flush(), "nwv_dstream_flush");
+}
+int nwv_dstream_stats(nwv_ctx* ctx, int ds, uint64_t out[8]) {
+    const auto s = ds_get(ctx, ds);
+    if (!s || !out) return set_err(NWV_ERR_ARG, "no such digest stream");
+    static_assert(nwv::DS_STATS == 8, "nwv_dstream_stats' out[8]");
+    s->core->stats(out);
+    return NWV_OK;
+}
+int nwv_dstream_close(nwv_ctx* ctx, int ds) {
+    if (nwv::ds_in_callback()) return set_err(NWV_ERR_REENTRANT, "nwv_dstream_close from a completion callback");
+    const auto s = ds_take(ctx, ds);
+    if (!s) return set_err(NWV_ERR_ARG, "no such digest stream");
+    return ds_rc(s->core->close(), "nwv_dstream_close");
 }
 
 }  // extern "C"

@@ -725,4 +725,44 @@ extern "C" {
     pub fn nwv_service_flush(svc: *mut NwvService) -> c_int;
     pub fn nwv_service_stats(svc: *mut NwvService, out: *mut u64) -> c_int;
     pub fn nwv_service_free(svc: *mut NwvService);
+    // ---- the digest stream (include/nwv_digest_stream.h) ----
+    pub fn nwv_dstream_open(
+        ctx: *mut NwvCtx,
+        device_index: c_int,
+        slice_blocks: usize,
+        pool_chunks: usize,
+        max_messages: usize,
+    ) -> c_int;
+    pub fn nwv_dstream_submit(
+        ctx: *mut NwvCtx,
+        ds: c_int,
+        data: *const u8,
+        len: usize,
+        digest_out: *mut u8,
+        done: NwvDoneFn,
+        user: *mut c_void,
+    ) -> c_int;
+    pub fn nwv_dstream_submit_serialized(
+        ctx: *mut NwvCtx,
+        ds: c_int,
+        buf: *const u8,
+        len: usize,
+        digest_out: *mut u8,
+        err_offset_out: *mut i64,
+        done: NwvDoneFn,
+        user: *mut c_void,
+    ) -> c_int;
+    pub fn nwv_dstream_begin(
+        ctx: *mut NwvCtx,
+        ds: c_int,
+        digest_out: *mut u8,
+        done: NwvDoneFn,
+        user: *mut c_void,
+        msg_id: *mut u64,
+    ) -> c_int;
+    pub fn nwv_dstream_update(ctx: *mut NwvCtx, ds: c_int, msg_id: u64, data: *const u8, len: usize) -> c_int;
+    pub fn nwv_dstream_finish(ctx: *mut NwvCtx, ds: c_int, msg_id: u64) -> c_int;
+    pub fn nwv_dstream_flush(ctx: *mut NwvCtx, ds: c_int) -> c_int;
+    pub fn nwv_dstream_stats(ctx: *mut NwvCtx, ds: c_int, out: *mut u64) -> c_int;
+    pub fn nwv_dstream_close(ctx: *mut NwvCtx, ds: c_int) -> c_int;
 }

@@ -25,6 +25,7 @@
 
 pub mod bls;
 pub mod core_drain;
+pub mod digest_stream;
 pub mod ffi;
 
 use std::ffi::CStr;
