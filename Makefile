@@ -47,7 +47,7 @@ hostemu: tests/_build/libhostemu.so tests/_build/libsvcstub.so tests/_build/libb
 	tests/_build/libblswbemu.so tests/_build/libblsmsgring.so tests/_build/libblsmremu.so \
 	tests/_build/libblsapkring.so tests/_build/libblsaremu.so tests/_build/libblskeybatch.so \
 	tests/_build/libblskbemu.so tests/_build/libblsademu.so tests/_build/libblswvemu.so \
-	tests/_build/libcombpassemu.so \
+	tests/_build/libcombpassemu.so tests/_build/libtypedfusedemu.so \
 	tests/_build/libtailrcemu.so tests/_build/liblanepool.so tests/_build/libdstream.so
 # the digest stream (digest_stream.h: chunk pool, hold-back rule, tick plan, pump, callbacks) over a stub
 # device that runs the work records with blake2b.h's compression (tests/test_digest_stream_host.py)
@@ -144,6 +144,13 @@ tests/_build/libcombemu.so: tests/hostemu/comb_hostemu.cpp $(CSRC)
 tests/_build/libcombpassemu.so: tests/hostemu/comb_pass_hostemu.cpp tests/hostemu/comb_hostemu.cpp $(CSRC)
 	@mkdir -p tests/_build
 	$(HIPCC) -std=c++17 -O1 --offload-host-only -x hip -DNWV_BOUNDS_CHECK -fPIC -shared -o $@ tests/hostemu/comb_pass_hostemu.cpp
+# the one-launch typed path on the host: the one-block BLAKE2b, the fused kernels' typed messages on the
+# comb emulation, and nwv_types.cpp over a stub engine that records its plan (tests/test_typed_fused_hostemu.py)
+tests/_build/libtypedfusedemu.so: tests/hostemu/typed_fused_hostemu.cpp tests/hostemu/comb_hostemu.cpp \
+		narwhal_amd/csrc/nwv_types.cpp include/nwv_types.h include/nwv_bls.h $(CSRC)
+	@mkdir -p tests/_build
+	$(HIPCC) -std=c++17 -O1 --offload-host-only -x hip -DNWV_BOUNDS_CHECK -fPIC -shared -o $@ \
+		tests/hostemu/typed_fused_hostemu.cpp narwhal_amd/csrc/nwv_types.cpp
 # the row kernel's per-signature arithmetic on the host (tests/test_each_row_hostemu.py)
 tests/_build/libeachemu.so: tests/hostemu/each_row_hostemu.cpp $(CSRC)
 	@mkdir -p tests/_build

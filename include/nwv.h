@@ -163,6 +163,23 @@ size_t nwv_comb_pass_max(const nwv_ctx* ctx);
  * them also counts as a per-signature pass in nwv_diag_counters out[2] and
  * nwv_diag_device_counters [8], and never as a comb batch), out[1] the signatures in those passes. */
 int nwv_diag_comb_pass(const nwv_ctx* ctx, uint64_t out[2]);
+/* Typed calls in one launch.  With a non-zero setting, a call of
+ * nwv_ed25519_verify_batch_typed -- and so every Header / Vote / Certificate verification of
+ * include/nwv_types.h -- that qualifies runs its digests and its signatures in ONE launch
+ * (k_ed_tiny_fused up to 64 signatures, k_ed_comb_fused up to nwv_comb_batch_max) instead of a
+ * BLAKE2b launch and a signature launch behind it.  A call qualifies when it is a whole
+ * single-device call (fewer signatures than the shard minimum: the setting never applies at or
+ * above it), every signing key has a comb table (nwv_keycache_register), no signature is over the
+ * digest of a side preimage, and the context was not opened with NWV_FLAG_NO_TINY,
+ * NWV_FLAG_MSM_ALWAYS or NWV_FLAG_MSM_NEVER.  Every other call takes the launches it takes with
+ * the setting off, and the results are the same bit for bit in both forms.  Default 0 (off). */
+int nwv_set_typed_fused(nwv_ctx* ctx, int on);
+int nwv_typed_fused(const nwv_ctx* ctx);
+/* Diagnostics, summed over the devices: out[0] launches of k_ed_tiny_fused (each also counts as a
+ * tiny batch in nwv_diag_counters out[0] and nwv_diag_device_counters [6]), out[1] launches of
+ * k_ed_comb_fused (each also a comb batch, nwv_diag_counters_ex [3] and device counter [9]),
+ * out[2] typed calls made with the setting on that took the two-launch form. */
+int nwv_diag_typed_fused(const nwv_ctx* ctx, uint64_t out[3]);
 /* HIP ordinal of the context's i-th device (-1 if out of range) */
 int nwv_device_ordinal(const nwv_ctx* ctx, int i);
 /* Placement: which device object of a multi-device context serves a call.  A call that does not
@@ -293,6 +310,23 @@ int nwv_ed25519_verify_batch_keyed_digests(nwv_ctx* ctx, size_t n_pre, const uin
                                            size_t n, const uint32_t* key_idx, const uint8_t* sig,
                                            const uint32_t* digest_idx, const uint8_t seed32[32],
                                            int* all_valid, uint64_t* verdict_bits_or_null);
+/* The typed sibling of nwv_ed25519_verify_batch_keyed_digests: signature i is over message
+ * msg_idx[i], where message m < n_pre is the BLAKE2b-256 digest of preimage m and message
+ * n_pre + k is the k-th of the n_lit literal 32-byte messages in lits (bytes the caller already
+ * holds: a header's id).  pre_short[m] != 0 marks preimage m as a short one: at most 128 bytes (a
+ * longer one counts as a side preimage), which the signature kernels may hash themselves; the
+ * others are side preimages, hashed for the host (a header's preimage, whose digest only the id
+ * comparison reads), and a signature over a side preimage's digest makes the call take the
+ * two-launch form.  digests_out receives every digest (n_pre x 32) in both forms; all_valid and
+ * the verdict bits are as the sibling's.  With nwv_set_typed_fused the call runs as one launch
+ * when it qualifies (see there); otherwise, and on every context with the setting off, it hashes
+ * all preimages with the BLAKE2b launch, places the literals behind the digests in the message
+ * arena and proceeds as the sibling does, so it is correct at every size. */
+int nwv_ed25519_verify_batch_typed(nwv_ctx* ctx, size_t n_pre, const uint8_t* pre_base, const uint64_t* pre_off,
+                                   const uint64_t* pre_len, const uint8_t* pre_short, uint8_t* digests_out,
+                                   size_t n_lit, const uint8_t* lits, size_t n_keys, const uint8_t* keys,
+                                   size_t n, const uint32_t* key_idx, const uint8_t* sig, const uint32_t* msg_idx,
+                                   const uint8_t seed32[32], int* all_valid, uint64_t* verdict_bits_or_null);
 
 /* Fill every device's committee key cache with n_keys keys (n_keys x 32), e.g. at epoch start
  * (Core::change_epoch, primary/src/core.rs:592-611).  Batch calls fill the cache themselves;

@@ -124,6 +124,12 @@ def load():
         "nwv_set_comb_pass_max": ([_vp, _sz], _i32),
         "nwv_comb_pass_max": ([_vp], _sz),
         "nwv_diag_comb_pass": ([_vp, _vp], _i32),
+        # typed calls in one launch (Engine.set_typed_fused, diag_typed_fused, verify_batch_typed)
+        "nwv_set_typed_fused": ([_vp, _i32], _i32),
+        "nwv_typed_fused": ([_vp], _i32),
+        "nwv_diag_typed_fused": ([_vp, _vp], _i32),
+        "nwv_ed25519_verify_batch_typed": ([_vp, _sz, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp, _vp,
+                                            _vp, _vp, _vp], _i32),
         "nwv_bls_set_apk_ring": ([_vp, _sz], _i32),
         "nwv_bls_apk_ring": ([_vp], _sz),
         "nwv_bls_last_apk": ([_vp, _vp], _i32),
@@ -353,6 +359,48 @@ class Engine:
         out = np.zeros(2, dtype=np.uint64)
         _check(self.lib.nwv_diag_comb_pass(self._h, out.ctypes.data))
         return int(out[0]), int(out[1])
+
+    def set_typed_fused(self, on):
+        """nwv_set_typed_fused: typed calls (header / vote / certificate verification) that qualify
+        run their digests and signatures in one launch (off by default)"""
+        _check(self.lib.nwv_set_typed_fused(self._h, 1 if on else 0))
+
+    @property
+    def typed_fused(self):
+        return bool(self.lib.nwv_typed_fused(self._h))
+
+    def diag_typed_fused(self):
+        """nwv_diag_typed_fused: (fused tiny launches, fused comb launches, typed calls made with the
+        setting on that took the two-launch form)"""
+        out = np.zeros(3, dtype=np.uint64)
+        _check(self.lib.nwv_diag_typed_fused(self._h, out.ctypes.data))
+        return int(out[0]), int(out[1]), int(out[2])
+
+    def verify_batch_typed(self, preimages, short, literals, keys, key_idx, sigs, msg_idx, want_bits=True):
+        """nwv_ed25519_verify_batch_typed: signature i by keys[key_idx[i]] over message msg_idx[i] --
+        m < len(preimages): the BLAKE2b-256 digest of preimage m (short[m]: a one-block preimage the
+        signature kernels may hash themselves); len(preimages) + k: the 32-byte literal k.
+        Returns (digests, all_valid, verdicts or None)."""
+        npre, n = len(preimages), len(sigs)
+        arena = np.frombuffer(b"".join(preimages) + bytes(16), dtype=np.uint8)
+        lens = np.array([len(p) for p in preimages], dtype=np.uint64)
+        offs = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.uint64) if npre else np.zeros(0, np.uint64)
+        sh = np.array([1 if s else 0 for s in short], dtype=np.uint8)
+        dig = np.zeros(32 * max(npre, 1), dtype=np.uint8)
+        lit = np.frombuffer(b"".join(literals) or bytes(32), dtype=np.uint8)
+        kb = np.frombuffer(b"".join(keys) or bytes(32), dtype=np.uint8)
+        ki = np.array(key_idx, dtype=np.uint32)
+        sg = np.frombuffer(b"".join(sigs) or bytes(64), dtype=np.uint8)
+        mi = np.array(msg_idx, dtype=np.uint32)
+        bits = np.zeros((n + 63) // 64 + 1, dtype=np.uint64)
+        ok = ctypes.c_int(0)
+        _check(self.lib.nwv_ed25519_verify_batch_typed(
+            self._h, npre, arena.ctypes.data, offs.ctypes.data, lens.ctypes.data, sh.ctypes.data, dig.ctypes.data,
+            len(literals), lit.ctypes.data, len(keys), kb.ctypes.data, n, ki.ctypes.data, sg.ctypes.data,
+            mi.ctypes.data, None, ctypes.byref(ok), bits.ctypes.data if want_bits else None))
+        digests = [dig[32 * j:32 * j + 32].tobytes() for j in range(npre)]
+        verdicts = [bool((int(bits[i >> 6]) >> (i & 63)) & 1) for i in range(n)] if want_bits else None
+        return digests, bool(ok.value), verdicts
 
     def diag_each_row_reuse(self):
         """nwv_diag_each_row_reuse: the row kernel's passes that reused a rejected MSM's records"""

@@ -98,4 +98,23 @@ NWV_HD void blake2b_digest256(const blake2b_state& s, uint32_t out[8]) {
     }
 }
 
+// BLAKE2b-256 of a preimage of at most one block (len <= 128; a longer one is cut to its first
+// 128 bytes) on one lane: the Vote::digest / Certificate::digest preimage (80 bytes) is a single
+// final compression.  p may be LDS or global memory, padded as every message arena is.  The
+// compression is k_blake2b_many's (blake2b_compress above).
+static constexpr uint32_t BLAKE2B_ONE_BLOCK_MAX = 128;
+NWV_HD void blake2b256_one_block(const uint8_t* p, uint32_t len, uint32_t out[8]) {
+    const uint32_t L = len < BLAKE2B_ONE_BLOCK_MAX ? len : BLAKE2B_ONE_BLOCK_MAX;
+    blake2b_state s;
+    blake2b_init256(s);
+    u64p m[16];
+#pragma unroll
+    for (int t = 0; t < 16; t++) {
+        m[t].lo = msg_word_trim(p, 8 * t, L);
+        m[t].hi = msg_word_trim(p, 8 * t + 4, L);
+    }
+    blake2b_compress(s, m, L, true);
+    blake2b_digest256(s, out);
+}
+
 }  // namespace nwv

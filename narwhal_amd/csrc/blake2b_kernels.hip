@@ -104,12 +104,28 @@ __device__ __forceinline__ uint64_t iv64(int k) {
 }
 }  // namespace
 
-extern "C" __global__ void __launch_bounds__(64) k_blake2b_quad(
-    uint64_t n, const uint8_t* __restrict__ base, const uint64_t* __restrict__ off,
-    const uint64_t* __restrict__ len, uint32_t* __restrict__ out, uint32_t* __restrict__ out2) {
-    __shared__ uint64_t blk[16][16];
-    const int lane = threadIdx.x, q = lane & 3, slot = lane >> 2;
-    const uint64_t i = (uint64_t)blockIdx.x * 16 + slot;
+// The quad form on one wave: messages 16 * group .. 16 * group + 15 of the call, blk = the wave's
+// 16 staged blocks in LDS.  BLOCK_SYNC: the wave is the whole workgroup (k_blake2b_quad) and the
+// staging is ordered by the workgroup barrier; otherwise (the digest workgroups of the fused typed
+// kernels, tiny_kernels.hip / comb_kernels.hip, where each wave runs groups of its own and waves
+// loop different numbers of times) by the wave's own in-order LDS pipe, with no barrier at all.
+template <bool BLOCK_SYNC>
+__device__ __forceinline__ void b2_quad_sync() {
+    if (BLOCK_SYNC) {
+        __syncthreads();
+    } else {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
+}
+template <bool BLOCK_SYNC>
+__device__ __forceinline__ void b2_quad_group(uint64_t (*blk)[16], int lane, uint64_t group, uint64_t n,
+                                              const uint8_t* __restrict__ base, const uint64_t* __restrict__ off,
+                                              const uint64_t* __restrict__ len, uint32_t* __restrict__ out,
+                                              uint32_t* __restrict__ out2) {
+    const int q = lane & 3, slot = lane >> 2;
+    const uint64_t i = group * 16 + slot;
     const bool active = i < n;
     const uint8_t* p = active ? base + off[i] : base;
     const uint64_t L = active ? len[i] : 0;
@@ -151,7 +167,7 @@ extern "C" __global__ void __launch_bounds__(64) k_blake2b_quad(
 #pragma unroll
         for (int t = 0; t < 4; t++) blk[slot][4 * q + t] = (uint64_t)w[2 * t] | ((uint64_t)w[2 * t + 1] << 32);
         if (b + 1 < nb) fetch(b + 1);
-        __syncthreads();
+        b2_quad_sync<BLOCK_SYNC>();
         // every sigma-selected word this lane needs for the 12 rounds, before the chain starts
         const uint64_t* m = blk[slot];
         uint64_t mw[12][4];
@@ -182,7 +198,7 @@ extern "C" __global__ void __launch_bounds__(64) k_blake2b_quad(
             h0 ^= va ^ vc;
             h1 ^= vb ^ vd;
         }
-        __syncthreads();
+        b2_quad_sync<BLOCK_SYNC>();
     }
     if (active) {
         out[8 * i + 2 * q] = (uint32_t)h0;
@@ -192,6 +208,35 @@ extern "C" __global__ void __launch_bounds__(64) k_blake2b_quad(
             out2[8 * i + 2 * q + 1] = (uint32_t)(h0 >> 32);
         }
     }
+}
+
+extern "C" __global__ void __launch_bounds__(64) k_blake2b_quad(
+    uint64_t n, const uint8_t* __restrict__ base, const uint64_t* __restrict__ off,
+    const uint64_t* __restrict__ len, uint32_t* __restrict__ out, uint32_t* __restrict__ out2) {
+    __shared__ uint64_t blk[16][16];
+    b2_quad_group<true>(blk, (int)threadIdx.x, (uint64_t)blockIdx.x, n, base, off, len, out, out2);
+}
+
+// The "side" digests of a fused typed call (k_ed_tiny_fused / k_ed_comb_fused): the workgroups
+// past the signature workgroups hash the call's long preimages with the quad form, B2_SIDE_WAVES
+// waves a workgroup and 16 messages a wave; later waves of the workgroup leave at once.  Nothing
+// here touches the verdict words or waits for anybody.
+static constexpr int B2_SIDE_WAVES = 2;
+struct B2SideArgs {
+    uint64_t n;            // side preimages (0: the launch has no digest workgroups)
+    const uint8_t* base;
+    const uint64_t* off;
+    const uint64_t* len;
+    uint32_t* out;         // device digests [n][8]
+    uint32_t* out2;        // coherent pinned host memory [n][8], or null
+};
+__device__ __forceinline__ void b2_side_block(const B2SideArgs& s, uint32_t block) {
+    __shared__ uint64_t sblk[B2_SIDE_WAVES][16][16];
+    const int wv = (int)(threadIdx.x >> 6);
+    if (wv >= B2_SIDE_WAVES) return;
+    const uint64_t group = (uint64_t)block * B2_SIDE_WAVES + (uint64_t)wv;
+    if (group * 16 >= s.n) return;  // (wave-uniform)
+    b2_quad_group<false>(sblk[wv], (int)(threadIdx.x & 63), group, s.n, s.base, s.off, s.len, s.out, s.out2);
 }
 
 namespace {

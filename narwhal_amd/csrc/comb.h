@@ -5,6 +5,7 @@
 // Everything here is __host__ __device__: the kernels call these functions and
 // tests/hostemu/comb_hostemu.cpp and comb_pass_hostemu.cpp run the same ones on the CPU.
 #pragma once
+#include "blake2b.h"
 #include "ed25519_lane.h"
 #include "msm.h"
 
@@ -53,6 +54,41 @@ NWV_HD bool comb_cross_equal(const uint32_t x[32]) {
     bool id = true;
     for (int q = 0; q < 8; q++) id = id && x[q] == x[8 + q] && x[16 + q] == x[24 + q];
     return id;
+}
+
+// ---- typed calls with their digests in the same launch (k_ed_tiny_fused, k_ed_comb_fused) ----
+// A signature of a typed call (Header / Vote / Certificate verification, nwv_types.cpp) signs
+// either bytes the host already holds (a header's id) or the BLAKE2b-256 of a preimage of at most
+// one block (Vote::digest, Certificate::digest: 80 bytes).  The fused kernels take the second kind
+// as the preimage itself: the lane that hashes R || A || M compresses it first (blake2b.h
+// blake2b256_one_block) and signs over the digest.  Signatures that share a preimage each
+// recompute the one compression; nobody waits for anybody.
+// src word of signature i: 0 = off[i] / len[i] name the literal message; otherwise they name the
+// preimage of short digest (src & ~TYPED_SRC_STORE) - 1, and with TYPED_SRC_STORE this signature
+// (the first that uses the digest) also stores it for the host.
+static constexpr uint32_t TYPED_SRC_STORE = 0x80000000u;
+static constexpr int TYPED_DBUF_WORDS = 16;  // the digest and the aligned over-read behind it
+struct TypedFusedArgs {
+    const uint32_t* src;   // [n]
+    uint32_t* short_out;   // coherent pinned host memory: [short digests][8]
+    uint32_t sig_blocks;   // workgroups that check signatures; the rest hash side preimages
+};
+// The message signature i is checked over: the literal (returned as it is), or the digest of the
+// preimage, written to dbuf (TYPED_DBUF_WORDS words the lane owns: LDS on the device) and, when the
+// src word asks, to short_out.
+NWV_HD const uint8_t* typed_message(uint32_t src, const uint8_t* msg, uint32_t& mlen, uint32_t* dbuf,
+                                    uint32_t* short_out) {
+    if (src == 0u) return msg;
+    uint32_t d[8];
+    blake2b256_one_block(msg, mlen, d);
+    for (int q = 0; q < 8; q++) dbuf[q] = d[q];
+    for (int q = 8; q < TYPED_DBUF_WORDS; q++) dbuf[q] = 0u;
+    if ((src & TYPED_SRC_STORE) && short_out) {
+        uint32_t* o = short_out + 8 * (size_t)((src & ~TYPED_SRC_STORE) - 1u);
+        for (int q = 0; q < 8; q++) o[q] = d[q];
+    }
+    mlen = 32u;
+    return reinterpret_cast<const uint8_t*>(dbuf);
 }
 
 // ---- k_ed_comb_pass (comb_kernels.hip): the same check with the comb sum walked by lanes ----

@@ -41,7 +41,11 @@ struct CombArgs {
 };
 
 static constexpr int COMB_WAVES = COMB_G + 1;
-extern "C" __global__ void __launch_bounds__(64 * COMB_WAVES) k_ed_comb(CombArgs a) {
+// FUSED (k_ed_comb_fused, a typed call with the setting nwv_set_typed_fused): signature i's message
+// is what typed_message (comb.h) makes of f.src[i], as in k_ed_tiny_fused.  The unfused
+// instantiation is k_ed_comb as it was.
+template <bool FUSED>
+__device__ __forceinline__ void ed_comb_block(const CombArgs& a, const TypedFusedArgs& f) {
 #if defined(__HIP_DEVICE_COMPILE__)
     __shared__ uint32_t rsh[COMB_G * 48];            // wave 0's rows (48 words each), then the cross products
     __shared__ uint32_t r8sh[48];                    // [8] R of one row on its way to ten-limb form
@@ -49,8 +53,9 @@ extern "C" __global__ void __launch_bounds__(64 * COMB_WAVES) k_ed_comb(CombArgs
     __shared__ int dg[COMB_G][2][COMB_TABLES];       // digits of s and of k
     __shared__ uint32_t hok[COMB_G];                 // s < l
     __shared__ uint32_t pts[COMB_G * 64 * P3_WORDS];  // each comb wave's 64 terms, summed in place
+    __shared__ uint32_t dmsg[FUSED ? COMB_G * TYPED_DBUF_WORDS : 1];  // FUSED: each hashing lane's digest
     const int t = threadIdx.x, wv = t >> 6, lane = t & 63;
-    const uint32_t base = blockIdx.x * COMB_G;  // grid = ceil(n / COMB_G); base < n
+    const uint32_t base = blockIdx.x * COMB_G;  // signature workgroups: ceil(n / COMB_G); base < n
     if (wv == 0 && lane < COMB_G) {
         const uint32_t i = base + lane;
         if (i < a.n) {
@@ -58,7 +63,10 @@ extern "C" __global__ void __launch_bounds__(64 * COMB_WAVES) k_ed_comb(CombArgs
             msm_load8(a.pk + 32 * (size_t)i, Aw);
             msm_load8(a.sig + 64 * (size_t)i, Rw);
             msm_load8(a.sig + 64 * (size_t)i + 32, Sw);
-            hok[lane] = comb_scalars(Aw, Rw, Sw, a.msg + a.off[i], a.len[i], dg[lane][0], dg[lane][1]) ? 1u : 0u;
+            const uint8_t* mp = a.msg + a.off[i];
+            uint32_t ml = a.len[i];
+            if (FUSED) mp = typed_message(f.src[i], mp, ml, dmsg + TYPED_DBUF_WORDS * lane, f.short_out);
+            hok[lane] = comb_scalars(Aw, Rw, Sw, mp, ml, dg[lane][0], dg[lane][1]) ? 1u : 0u;
         }
     }
     __syncthreads();  // digits in LDS
@@ -151,6 +159,19 @@ extern "C" __global__ void __launch_bounds__(64 * COMB_WAVES) k_ed_comb(CombArgs
         }
     }
 #endif
+}
+
+extern "C" __global__ void __launch_bounds__(64 * COMB_WAVES) k_ed_comb(CombArgs a) {
+    ed_comb_block<false>(a, TypedFusedArgs{});
+}
+// A typed call above TINY_MAX in one launch: workgroups [0, f.sig_blocks) are k_ed_comb's over
+// typed messages, the workgroups behind them hash the side preimages (k_ed_tiny_fused's layout).
+extern "C" __global__ void __launch_bounds__(64 * COMB_WAVES) k_ed_comb_fused(CombArgs a, TypedFusedArgs f, B2SideArgs s) {
+    if (blockIdx.x >= f.sig_blocks) {
+        b2_side_block(s, blockIdx.x - f.sig_blocks);
+        return;
+    }
+    ed_comb_block<true>(a, f);
 }
 
 // ---- the comb check as a per-signature pass behind a rejected batch MSM (k_ed_comb_pass) ----

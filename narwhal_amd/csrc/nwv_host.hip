@@ -287,6 +287,9 @@ struct Gpu {
     // did (nwv_diag_comb_pass): passes, signatures
     std::atomic<size_t> comb_pass_max{0};
     std::atomic<uint64_t> n_comb_pass{0}, n_comb_pass_sigs{0};
+    // typed calls with the setting nwv_set_typed_fused (nwv_diag_typed_fused): launches of
+    // k_ed_tiny_fused, of k_ed_comb_fused, and calls that asked for them and took the fallback form
+    std::atomic<uint64_t> n_tf_tiny{0}, n_tf_comb{0}, n_tf_fallback{0};
 };
 
 int with_device(Lane& d) {
@@ -1066,7 +1069,8 @@ struct KeyedTail {
 
 int ed_stage(Lane& d, EdBuffers& b, size_t lo, size_t hi, const uint8_t* pk, const uint8_t* sig,
              const uint8_t* msg_base, const uint64_t* msg_off, const uint32_t* msg_len,
-             const uint8_t* seed32, const KeyedTail* kt = nullptr, const DevBuf* dev_msg = nullptr) {
+             const uint8_t* seed32, const KeyedTail* kt = nullptr, const DevBuf* dev_msg = nullptr,
+             size_t msg_span = 0) {
     const size_t n = hi - lo;
     uint64_t mlo = UINT64_MAX, mhi = 0;
     for (size_t i = lo; i < hi; i++) {
@@ -1074,6 +1078,13 @@ int ed_stage(Lane& d, EdBuffers& b, size_t lo, size_t hi, const uint8_t* pk, con
         mhi = std::max<uint64_t>(mhi, msg_off[i] + msg_len[i]);
     }
     if (n == 0 || mhi < mlo) { mlo = 0; mhi = 0; }
+    // msg_span: the first msg_span bytes of msg_base go as they are (a typed call's arena holds
+    // tables behind the messages, at offsets the kernels are given)
+    if (msg_span) {
+        if (mhi > msg_span) return set_err(NWV_ERR_ARG, "message past the arena span");
+        mlo = 0;
+        mhi = msg_span;
+    }
     // dev_msg: the messages are already on the device (offsets index it as they are)
     if (dev_msg) {
         if (mhi + MSG_PAD > dev_msg->cap) return set_err(NWV_ERR_ARG, "device message offset out of range");
@@ -1343,7 +1354,7 @@ int ed_stage_keyed(Lane& d, EdBuffers& b, size_t lo, size_t hi, size_t n_keys, c
                    const uint32_t* key_idx, const uint8_t* sig, const uint8_t* msg_base,
                    const uint64_t* msg_off, const uint32_t* msg_len, const uint8_t* seed32,
                    const DevBuf* dev_msg = nullptr, bool kc_lookup_only = false, size_t comb_max = 0,
-                   std::vector<uint32_t>* pin_out = nullptr) {
+                   std::vector<uint32_t>* pin_out = nullptr, size_t msg_span = 0) {
     const size_t n = hi - lo;
     // per-thread scratch reused across calls (fresh large vectors are page-faulted in every call)
     thread_local std::vector<uint32_t> local, cnt, kid, koff, ksig, cur;
@@ -1409,7 +1420,8 @@ int ed_stage_keyed(Lane& d, EdBuffers& b, size_t lo, size_t hi, size_t n_keys, c
             kt.pass_only = n > comb_max;
         }
     }
-    rc = ed_stage(d, b, 0, n, pk.data(), sig + 64 * lo, msg_base, msg_off + lo, msg_len + lo, seed32, &kt, dev_msg);
+    rc = ed_stage(d, b, 0, n, pk.data(), sig + 64 * lo, msg_base, msg_off + lo, msg_len + lo, seed32, &kt, dev_msg,
+                  msg_span);
     if (rc) return rc;
     // the one-launch path: few signatures, every key registered (comb table present)
     if (n && n <= (size_t)TINY_MAX && !kslot.empty() && !(d.flags & (NWV_FLAG_NO_TINY | NWV_FLAG_MSM_NEVER))) {
@@ -1481,6 +1493,9 @@ struct nwv_ctx {
     // rejected registered-key batches of at most comb_pass_max signatures name their bad set with
     // k_ed_comb_pass (nwv_set_comb_pass_max, same clamp; every device object holds a copy)
     std::atomic<size_t> comb_pass_max{NWV_COMB_PASS_MAX_DEFAULT};
+    // typed calls (nwv_ed25519_verify_batch_typed) below shard_min signatures whose messages need
+    // no digest from another launch run as one launch (nwv_set_typed_fused; 0: off, the default)
+    std::atomic<int> typed_fused{0};
     // calls of at most latency_max signatures (digest calls: messages, and at most
     // latency_digest_bytes input bytes) lease from their device's reserved lanes
     // (nwv_set_latency_max, same clamp; 0: off, the default)
@@ -1729,6 +1744,23 @@ int nwv_set_comb_pass_max(nwv_ctx* ctx, size_t n) {
     return NWV_OK;
 }
 size_t nwv_comb_pass_max(const nwv_ctx* ctx) { return ctx ? ctx->comb_pass_max.load() : 0; }
+int nwv_set_typed_fused(nwv_ctx* ctx, int on) {
+    if (!ctx) return set_err(NWV_ERR_ARG, "null context");
+    // (nothing to clamp: a call of shard_min signatures or more never qualifies, see the entry)
+    ctx->typed_fused = on ? 1 : 0;
+    return NWV_OK;
+}
+int nwv_typed_fused(const nwv_ctx* ctx) { return ctx ? ctx->typed_fused.load() : 0; }
+int nwv_diag_typed_fused(const nwv_ctx* ctx, uint64_t out[3]) {
+    if (!ctx || !out) return set_err(NWV_ERR_ARG, "null argument");
+    out[0] = out[1] = out[2] = 0;
+    for (const Gpu* g : ctx->devs) {
+        out[0] += g->n_tf_tiny.load();
+        out[1] += g->n_tf_comb.load();
+        out[2] += g->n_tf_fallback.load();
+    }
+    return NWV_OK;
+}
 int nwv_set_latency_max(nwv_ctx* ctx, int engine, size_t n) {
     if (!ctx) return set_err(NWV_ERR_ARG, "null context");
     if (engine == NWV_ENGINE_BLS) return nwv_bls_set_latency_max(ctx, n);
@@ -1899,9 +1931,22 @@ static void set_ones(uint64_t* bits, size_t lo, size_t hi) {
     for (size_t i = lo; i < hi; i++) bits[i >> 6] |= 1ULL << (i & 63);
 }
 
+// What a typed call in the fused form adds to the launch of k_ed_tiny / k_ed_comb: the signatures'
+// src words and the short digests' host array, and the side preimages that the workgroups behind
+// the signatures' hash (typed_fused_run fills it; sig_blocks is set at the launch)
+struct TypedLaunch {
+    TypedFusedArgs f;
+    B2SideArgs s;
+};
+static unsigned typed_side_blocks(const TypedLaunch& tf) {
+    return (unsigned)((tf.s.n + 16 * B2_SIDE_WAVES - 1) / (16 * B2_SIDE_WAVES));
+}
+
 // k_ed_tiny over a staged tiny keyed batch (b.tiny): every signature's verdict in one launch,
-// read back through the lane's polled host word (or the workspace when the lane has none)
-static int tiny_on_device(Lane& d, EdBuffers& b, size_t n, hipStream_t stream, int* ok, uint64_t* bits) {
+// read back through the lane's polled host word (or the workspace when the lane has none).
+// tf: the call is a typed one in the fused form (k_ed_tiny_fused)
+static int tiny_on_device(Lane& d, EdBuffers& b, size_t n, hipStream_t stream, int* ok, uint64_t* bits,
+                          const TypedLaunch* tf = nullptr) {
     int rc;
     if (!d.tiny_ws.p) {
         if ((rc = d.tiny_ws.ensure(64))) return rc;
@@ -1935,7 +1980,14 @@ static int tiny_on_device(Lane& d, EdBuffers& b, size_t n, hipStream_t stream, i
         NWV_HIP(hipMemsetAsync(b.m_stamps.p, 0, 64, stream));
         a.stamps = b.m_stamps.as<unsigned long long>();
     }
-    hipLaunchKernelGGL(k_ed_tiny, dim3((unsigned)n), dim3(64 * TINY_WAVES), 0, stream, a);
+    if (tf) {
+        TypedFusedArgs f = tf->f;
+        f.sig_blocks = (uint32_t)n;
+        hipLaunchKernelGGL(k_ed_tiny_fused, dim3((unsigned)n + typed_side_blocks(*tf)), dim3(64 * TINY_WAVES), 0,
+                           stream, a, f, tf->s);
+    } else {
+        hipLaunchKernelGGL(k_ed_tiny, dim3((unsigned)n), dim3(64 * TINY_WAVES), 0, stream, a);
+    }
     if (hipGetLastError() != hipSuccess) {
         (void)hipStreamSynchronize(stream);
         return set_err(NWV_ERR_HIP, "k_ed_tiny launch");
@@ -1981,7 +2033,8 @@ static int tiny_on_device(Lane& d, EdBuffers& b, size_t n, hipStream_t stream, i
 // verdict in one launch.  The batch verdict comes back through the lane's polled host word (or
 // the workspace when the lane has none); the verdict words are copied back only for a rejected
 // batch whose caller asked for them.
-static int comb_on_device(Lane& d, EdBuffers& b, size_t n, hipStream_t stream, int* ok, uint64_t* bits) {
+static int comb_on_device(Lane& d, EdBuffers& b, size_t n, hipStream_t stream, int* ok, uint64_t* bits,
+                          const TypedLaunch* tf = nullptr) {
     int rc;
     const size_t words = (n + 63) / 64;
     // workspace: 64 bytes (arrivals, batch verdict), the accumulated words, the result words
@@ -2013,7 +2066,15 @@ static int comb_on_device(Lane& d, EdBuffers& b, size_t n, hipStream_t stream, i
     if (d.hseq == 0) d.hseq = 1;
     a.hseq = d.hseq;
     if (hv) __atomic_store_n(hv, 0u, __ATOMIC_RELEASE);
-    hipLaunchKernelGGL(k_ed_comb, dim3((unsigned)((n + COMB_G - 1) / COMB_G)), dim3(64 * COMB_WAVES), 0, stream, a);
+    const unsigned sig_blocks = (unsigned)((n + COMB_G - 1) / COMB_G);
+    if (tf) {
+        TypedFusedArgs f = tf->f;
+        f.sig_blocks = sig_blocks;
+        hipLaunchKernelGGL(k_ed_comb_fused, dim3(sig_blocks + typed_side_blocks(*tf)), dim3(64 * COMB_WAVES), 0, stream,
+                           a, f, tf->s);
+    } else {
+        hipLaunchKernelGGL(k_ed_comb, dim3(sig_blocks), dim3(64 * COMB_WAVES), 0, stream, a);
+    }
     if (hipGetLastError() != hipSuccess) {
         (void)hipStreamSynchronize(stream);
         return set_err(NWV_ERR_HIP, "k_ed_comb launch");
@@ -3092,17 +3153,21 @@ int nwv_blake2b256_many(nwv_ctx* ctx, size_t n, const uint8_t* base, const uint6
     });
 }
 
-int nwv_ed25519_verify_batch_keyed_digests(nwv_ctx* ctx, size_t n_pre, const uint8_t* pre_base,
-                                           const uint64_t* pre_off, const uint64_t* pre_len,
-                                           uint8_t* digests_out, size_t n_keys, const uint8_t* keys,
-                                           size_t n, const uint32_t* key_idx, const uint8_t* sig,
-                                           const uint32_t* digest_idx, const uint8_t seed32[32],
-                                           int* all_valid, uint64_t* verdict_bits_or_null) {
-    if (!ctx || !all_valid || (n_pre && (!pre_off || !pre_len || !digests_out)) ||
+// Digests, then the signatures over them, on the existing kernels: the hash launch and the
+// signature launch behind it on one stream (nwv_ed25519_verify_batch_keyed_digests, and the
+// fallback form of nwv_ed25519_verify_batch_typed).  Message i is digest digest_idx[i], or, from
+// n_pre on, literal digest_idx[i] - n_pre of the n_lit 32-byte literals: they are placed behind
+// the digests in the message arena.
+static int keyed_digests_run(nwv_ctx* ctx, size_t n_pre, const uint8_t* pre_base, const uint64_t* pre_off,
+                             const uint64_t* pre_len, uint8_t* digests_out, size_t n_lit, const uint8_t* lits,
+                             size_t n_keys, const uint8_t* keys, size_t n, const uint32_t* key_idx,
+                             const uint8_t* sig, const uint32_t* digest_idx, const uint8_t seed32[32],
+                             int* all_valid, uint64_t* verdict_bits_or_null) {
+    if (!ctx || !all_valid || (n_pre && (!pre_off || !pre_len || !digests_out)) || (n_lit && !lits) ||
         (n && (!keys || !key_idx || !sig || !digest_idx)))
         return set_err(NWV_ERR_ARG, "null argument");
     for (size_t i = 0; i < n; i++)
-        if (digest_idx[i] >= n_pre) return set_err(NWV_ERR_ARG, "digest index out of range");
+        if (digest_idx[i] >= n_pre + n_lit) return set_err(NWV_ERR_ARG, "digest index out of range");
     *all_valid = 1;
     // message i = digest digest_idx[i]: 32 bytes at 32 * digest_idx[i] of the digest array
     thread_local std::vector<uint64_t> moff;
@@ -3115,7 +3180,15 @@ int nwv_ed25519_verify_batch_keyed_digests(nwv_ctx* ctx, size_t n_pre, const uin
         // signatures are sharded (a smaller one stays fused on one device, placed by load, below)
         int rc = nwv_blake2b256_many(ctx, n_pre, pre_base, pre_off, pre_len, digests_out);
         if (rc || n == 0) return rc;
-        return nwv_ed25519_verify_batch_keyed(ctx, n_keys, keys, n, key_idx, sig, digests_out, moff.data(),
+        const uint8_t* hmsg = digests_out;
+        thread_local std::vector<uint8_t> joined;
+        if (n_lit) {  // the host's message array: the digests, the literals behind them
+            joined.resize(32 * (n_pre + n_lit));
+            if (n_pre) std::memcpy(joined.data(), digests_out, 32 * n_pre);
+            std::memcpy(joined.data() + 32 * n_pre, lits, 32 * n_lit);
+            hmsg = joined.data();
+        }
+        return nwv_ed25519_verify_batch_keyed(ctx, n_keys, keys, n, key_idx, sig, hmsg, moff.data(),
                                               mlen.data(), seed32, all_valid, verdict_bits_or_null);
     }
     static const uint8_t empty[1] = {0};
@@ -3132,7 +3205,9 @@ int nwv_ed25519_verify_batch_keyed_digests(nwv_ctx* ctx, size_t n_pre, const uin
     if (rc) return rc;
     // the digests stay on the device as the message arena of the batch; the over-read slack past
     // them needs no particular contents (SHA-512 and BLAKE2b mask the bytes past a message)
-    if ((rc = d.b2_out.ensure(32 * n_pre + 4 * MSG_PAD))) return rc;
+    if ((rc = d.b2_out.ensure(32 * (n_pre + n_lit) + 4 * MSG_PAD))) return rc;
+    if (n_lit)
+        NWV_HIP(hipMemcpyAsync(d.b2_out.as<uint8_t>() + 32 * n_pre, lits, 32 * n_lit, hipMemcpyHostToDevice, d.stream));
     uint64_t maxlen = 0;
     for (size_t k = 0; k < n_pre; k++) maxlen = std::max<uint64_t>(maxlen, pre_len[k]);
     // the batch is staged before the hash launch (its copy does not depend on the digests), so
@@ -3152,6 +3227,165 @@ int nwv_ed25519_verify_batch_keyed_digests(nwv_ctx* ctx, size_t n_pre, const uin
     kc_call_done(d);
     std::memcpy(digests_out, d.b2dig.p, 32 * n_pre);
     return NWV_OK;
+}
+
+int nwv_ed25519_verify_batch_keyed_digests(nwv_ctx* ctx, size_t n_pre, const uint8_t* pre_base,
+                                           const uint64_t* pre_off, const uint64_t* pre_len,
+                                           uint8_t* digests_out, size_t n_keys, const uint8_t* keys,
+                                           size_t n, const uint32_t* key_idx, const uint8_t* sig,
+                                           const uint32_t* digest_idx, const uint8_t seed32[32],
+                                           int* all_valid, uint64_t* verdict_bits_or_null) {
+    return keyed_digests_run(ctx, n_pre, pre_base, pre_off, pre_len, digests_out, 0, nullptr, n_keys, keys, n,
+                             key_idx, sig, digest_idx, seed32, all_valid, verdict_bits_or_null);
+}
+
+// The fused form of a typed call on lane d: one launch of k_ed_tiny_fused or k_ed_comb_fused.
+// The call's arena -- the literals, the preimage bytes, then the side list's offsets and lengths
+// and the signatures' src words -- is the staged batch's message arena (ed_stage's msg_span).
+// *took = 0: the staged batch did not qualify (a key without a comb table); nothing was launched.
+static int typed_fused_run(nwv_ctx* ctx, Lane& d, size_t n_pre, const uint8_t* pre_base, const uint64_t* pre_off,
+                           const uint64_t* pre_len, const uint8_t* pre_short, uint8_t* digests_out, size_t n_lit,
+                           const uint8_t* lits, size_t n_keys, const uint8_t* keys, size_t n,
+                           const uint32_t* key_idx, const uint8_t* sig, const uint32_t* msg_idx,
+                           const uint8_t seed[32], int* all_valid, uint64_t* bits, int* took) {
+    *took = 0;
+    auto is_short = [&](size_t j) { return pre_short[j] && pre_len[j] <= nwv::BLAKE2B_ONE_BLOCK_MAX; };
+    uint64_t plo = UINT64_MAX, phi = 0;
+    for (size_t j = 0; j < n_pre; j++) {
+        plo = std::min<uint64_t>(plo, pre_off[j]);
+        phi = std::max<uint64_t>(phi, pre_off[j] + pre_len[j]);
+    }
+    if (phi < plo) plo = phi = 0;
+    thread_local std::vector<uint8_t> ar;
+    thread_local std::vector<uint64_t> moff;
+    thread_local std::vector<uint32_t> mlen, first, side_j;
+    // which short preimages a signature names (first[j] = the first that does): the others, and
+    // every side preimage, go to the digest workgroups
+    first.assign(n_pre, UINT32_MAX);
+    for (size_t i = 0; i < n; i++)
+        if (msg_idx[i] < n_pre && first[msg_idx[i]] == UINT32_MAX) first[msg_idx[i]] = (uint32_t)i;
+    side_j.clear();
+    for (size_t j = 0; j < n_pre; j++)
+        if (!is_short(j) || first[j] == UINT32_MAX) side_j.push_back((uint32_t)j);
+    const size_t ns = side_j.size();
+    auto up8 = [](size_t x) { return (x + 7) & ~(size_t)7; };
+    // (the quad form fetches whole 128-byte blocks: 192 bytes of slack behind the preimages)
+    const size_t o_pre = 32 * n_lit, o_soff = up8(o_pre + (size_t)(phi - plo) + 192), o_slen = o_soff + 8 * ns,
+                 o_src = o_slen + 8 * ns, span = o_src + 4 * n;
+    ar.assign(span, 0);
+    if (n_lit) std::memcpy(ar.data(), lits, 32 * n_lit);
+    if (phi > plo) std::memcpy(ar.data() + o_pre, pre_base + plo, (size_t)(phi - plo));
+    uint64_t* soff = reinterpret_cast<uint64_t*>(ar.data() + o_soff);
+    uint64_t* slen = reinterpret_cast<uint64_t*>(ar.data() + o_slen);
+    for (size_t k = 0; k < ns; k++) {
+        soff[k] = o_pre + (pre_off[side_j[k]] - plo);
+        slen[k] = pre_len[side_j[k]];
+    }
+    uint32_t* src = reinterpret_cast<uint32_t*>(ar.data() + o_src);
+    moff.resize(n);
+    mlen.resize(n);
+    for (size_t i = 0; i < n; i++) {
+        const uint32_t m = msg_idx[i];
+        if (m >= n_pre) {
+            moff[i] = 32ull * (m - n_pre);
+            mlen[i] = 32u;
+            src[i] = 0u;
+        } else {
+            moff[i] = o_pre + (pre_off[m] - plo);
+            mlen[i] = (uint32_t)pre_len[m];
+            src[i] = (m + 1u) | (first[m] == (uint32_t)i ? nwv::TYPED_SRC_STORE : 0u);
+        }
+    }
+    int rc = ed_stage_keyed(d, d.ed, 0, n, n_keys, keys, key_idx, sig, ar.data(), moff.data(), mlen.data(), seed,
+                            nullptr, false, ctx->comb_batch_max.load(), nullptr, span);
+    if (rc) return rc;
+    const bool tiny = n <= (size_t)TINY_MAX;
+    if (tiny ? !d.ed.tiny : !d.ed.comb) return NWV_OK;
+    // the digests come back in coherent pinned memory: slot j of the first n_pre for a short digest
+    // that a signature stored, slot n_pre + k for entry k of the side list
+    if ((rc = d.b2dig.ensure(32 * (n_pre + ns) + 32, hipHostMallocCoherent | hipHostMallocMapped)) ||
+        (rc = d.b2_out.ensure(32 * ns + 32)))
+        return rc;
+    const uint8_t* g = d.ed.msg.as<uint8_t>();
+    TypedLaunch tf{};
+    tf.f.src = reinterpret_cast<const uint32_t*>(g + o_src);
+    tf.f.short_out = static_cast<uint32_t*>(d.b2dig.p);
+    tf.s.n = ns;
+    tf.s.base = g;
+    tf.s.off = reinterpret_cast<const uint64_t*>(g + o_soff);
+    tf.s.len = reinterpret_cast<const uint64_t*>(g + o_slen);
+    tf.s.out = d.b2_out.as<uint32_t>();
+    tf.s.out2 = static_cast<uint32_t*>(d.b2dig.p) + 8 * n_pre;
+    int ok = 1;
+    if (tiny) {
+        d.gpu->n_tiny++;
+        d.gpu->n_tf_tiny++;
+        rc = tiny_on_device(d, d.ed, n, d.stream, &ok, bits, &tf);
+    } else {
+        d.gpu->n_comb++;
+        d.gpu->n_tf_comb++;
+        rc = comb_on_device(d, d.ed, n, d.stream, &ok, bits, &tf);
+    }
+    if (rc) return rc;
+    // the verdict word comes from the last signature workgroup; the digest workgroups may still be
+    // running: the stream's completion covers them (and every digest store)
+    NWV_HIP(hipStreamSynchronize(d.stream));
+    kc_call_done(d);
+    if (!ok) *all_valid = 0;
+    const uint8_t* hd = static_cast<const uint8_t*>(d.b2dig.p);
+    for (size_t j = 0; j < n_pre; j++)
+        if (is_short(j) && first[j] != UINT32_MAX) std::memcpy(digests_out + 32 * j, hd + 32 * j, 32);
+    for (size_t k = 0; k < ns; k++) std::memcpy(digests_out + 32 * (size_t)side_j[k], hd + 32 * (n_pre + k), 32);
+    *took = 1;
+    return NWV_OK;
+}
+
+int nwv_ed25519_verify_batch_typed(nwv_ctx* ctx, size_t n_pre, const uint8_t* pre_base, const uint64_t* pre_off,
+                                   const uint64_t* pre_len, const uint8_t* pre_short, uint8_t* digests_out,
+                                   size_t n_lit, const uint8_t* lits, size_t n_keys, const uint8_t* keys,
+                                   size_t n, const uint32_t* key_idx, const uint8_t* sig, const uint32_t* msg_idx,
+                                   const uint8_t seed32[32], int* all_valid, uint64_t* verdict_bits_or_null) {
+    if (!ctx || !all_valid || (n_pre && (!pre_off || !pre_len || !pre_short || !digests_out)) || (n_lit && !lits) ||
+        (n && (!keys || !key_idx || !sig || !msg_idx)))
+        return set_err(NWV_ERR_ARG, "null argument");
+    if (n_pre + n_lit >= (size_t)0x7fffffff) return set_err(NWV_ERR_ARG, "too many messages");
+    for (size_t i = 0; i < n; i++)
+        if (msg_idx[i] >= n_pre + n_lit) return set_err(NWV_ERR_ARG, "message index out of range");
+    for (size_t j = 0; j < n_pre; j++)
+        if (pre_len[j] && !pre_base) return set_err(NWV_ERR_ARG, "null pre_base");
+    if (ctx->typed_fused.load()) {
+        // the one-launch form: a whole single-device call within the tiny or comb limits whose
+        // messages need no digest from another launch, on a context whose flags force no path;
+        // whether every key has its comb table shows when the batch is staged
+        bool fit = n > 0 && nwv::ed_shard_ranges(n, ctx->devs.size(), ctx->shard_min).size() == 1 &&
+                   (n <= (size_t)TINY_MAX || n <= ctx->comb_batch_max.load());
+        for (size_t i = 0; i < n && fit; i++) {
+            const uint32_t m = msg_idx[i];
+            fit = m >= n_pre || (pre_short[m] && pre_len[m] <= nwv::BLAKE2B_ONE_BLOCK_MAX);
+        }
+        Gpu* counted = ctx->devs[0];
+        if (fit) {
+            uint8_t seed[32];
+            fill_seed(seed32, seed);
+            const nwv::Ticket ticket(*ctx->place, (uint64_t)n);
+            counted = ctx->devs[ticket.dev()];
+            LaneRef lane(*counted, n <= ctx->latency_max.load());  // (a signature call)
+            Lane& d = *lane;
+            int rc = lane.rc();
+            if (rc) return rc;
+            if (!(d.flags & (NWV_FLAG_NO_TINY | NWV_FLAG_MSM_ALWAYS | NWV_FLAG_MSM_NEVER))) {
+                int took = 0;
+                *all_valid = 1;
+                rc = typed_fused_run(ctx, d, n_pre, pre_base, pre_off, pre_len, pre_short, digests_out, n_lit, lits,
+                                     n_keys, keys, n, key_idx, sig, msg_idx, seed, all_valid, verdict_bits_or_null,
+                                     &took);
+                if (rc || took) return rc;
+            }
+        }
+        counted->n_tf_fallback++;
+    }
+    return keyed_digests_run(ctx, n_pre, pre_base, pre_off, pre_len, digests_out, n_lit, lits, n_keys, keys, n,
+                             key_idx, sig, msg_idx, seed32, all_valid, verdict_bits_or_null);
 }
 
 int nwv_batch_digest_serialized(nwv_ctx* ctx, size_t n, const uint8_t* base, const uint64_t* off,

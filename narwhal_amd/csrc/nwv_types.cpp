@@ -70,13 +70,18 @@ void id_round_epoch_origin(const uint8_t* id, uint64_t round, uint64_t epoch, co
 struct DigestBatch {
     std::vector<uint8_t> arena;
     std::vector<uint64_t> off, len;
+    // one-block preimages whose digests signatures are over (votes, certificates): the typed engine
+    // call may hash those inside its signature kernels (nwv_ed25519_verify_batch_typed pre_short)
+    std::vector<uint8_t> is_short;
     void reset() {
         arena.clear();
         off.clear();
         len.clear();
+        is_short.clear();
     }
-    size_t add_begin() {
+    size_t add_begin(bool short_preimage = false) {
         off.push_back(arena.size());
+        is_short.push_back(short_preimage ? 1 : 0);
         return off.size() - 1;
     }
     void add_end() { len.push_back(arena.size() - off.back()); }
@@ -236,18 +241,34 @@ namespace {
 // (nwv_ed25519_verify_batch_keyed_digests).  A header's signature is checked over its computed
 // digest: whenever that verdict is used the id equals the digest (else InvalidHeaderId comes
 // first), so the bytes are the ones the reference verifies.
+// With the engine's setting nwv_set_typed_fused (typed: the plan is for
+// nwv_ed25519_verify_batch_typed) a header's signature is checked over the caller's id instead, a
+// literal the host already holds: by the same invariant the verdict is only read when the id is
+// the digest.  Nothing on the device then waits for a header preimage's digest, and the vote and
+// certificate preimages are marked short, so a call that qualifies is one launch.
 struct DigestSigBatch {
+    static constexpr uint32_t LITERAL = 0x80000000u;  // didx: literal k of lits (typed plans only)
     const nwv_committee* c = nullptr;
-    std::vector<uint8_t> keys, sig, ok;
+    bool typed = false;
+    std::vector<uint8_t> keys, sig, ok, lits;
     std::vector<uint32_t> kidx, didx;
     std::vector<uint64_t> bits;
-    void reset(const nwv_committee* cm) {
+    void reset(const nwv_committee* cm, bool typed_plan) {
         c = cm;
+        typed = typed_plan;
         keys.clear();
         sig.clear();
+        lits.clear();
         kidx.clear();
         didx.clear();
         if (c && c->n) keys.assign(c->keys, c->keys + 32 * c->n);
+    }
+    // a header's signature: over its digest (by index), or in a typed plan over its id
+    size_t add_header(const uint8_t* p, const uint8_t* s, size_t digest, const uint8_t* id) {
+        if (!typed) return add(p, s, digest);
+        const size_t k = lits.size() / 32;
+        put(lits, id, 32);
+        return add(p, s, LITERAL | k);
     }
     size_t add_run(const size_t* ks, size_t q, const uint8_t* s, size_t digest) {
         const size_t first = kidx.size();
@@ -278,9 +299,19 @@ struct DigestSigBatch {
         // the one-launch path (k_ed_tiny) inside the engine call below
         int rc = (c && c->n) ? nwv_keycache_register(ctx, c->n, c->keys) : NWV_OK;
         if (rc) return rc;
-        rc = nwv_ed25519_verify_batch_keyed_digests(ctx, m, db.arena.data(), db.off.data(), db.len.data(),
+        if (typed) {
+            // message index: a digest's as it is, literal k behind the m digests
+            for (size_t i = 0; i < n; i++)
+                if (didx[i] & LITERAL) didx[i] = (uint32_t)m + (didx[i] & ~LITERAL);
+            rc = nwv_ed25519_verify_batch_typed(ctx, m, db.arena.data(), db.off.data(), db.len.data(),
+                                                db.is_short.data(), dig.data(), lits.size() / 32, lits.data(),
+                                                keys.size() / 32, keys.data(), n, kidx.data(), sig.data(), didx.data(),
+                                                nullptr, &all, bits.data());
+        } else {
+            rc = nwv_ed25519_verify_batch_keyed_digests(ctx, m, db.arena.data(), db.off.data(), db.len.data(),
                                                         dig.data(), keys.size() / 32, keys.data(), n, kidx.data(),
                                                         sig.data(), didx.data(), nullptr, &all, bits.data());
+        }
         if (rc) return rc;
         for (size_t i = 0; i < n; i++) ok[i] = (uint8_t)((bits[i >> 6] >> (i & 63)) & 1);
         return NWV_OK;
@@ -304,16 +335,17 @@ int verify_mixed(nwv_ctx* ctx, const nwv_committee& c, size_t nh, const nwv_head
     thread_local DigestBatch db;
     thread_local DigestSigBatch sb;
     db.reset();
-    sb.reset(&c);
+    sb.reset(&c, nwv_typed_fused(ctx) != 0);
     std::vector<HeaderPlan> hplan(nh), cplan(nc);
     for (size_t i = 0; i < nh; i++) {
         plan_header(c, h[i], db, hplan[i]);
-        if (!hplan[i].pre && !hplan[i].post) hplan[i].sig = (long)sb.add(h[i].author, h[i].signature, hplan[i].digest);
+        if (!hplan[i].pre && !hplan[i].post)
+            hplan[i].sig = (long)sb.add_header(h[i].author, h[i].signature, hplan[i].digest, h[i].id);
     }
     htrace("mixed:headers");
     std::vector<long> vsig(nv, -1);
     for (size_t i = 0; i < nv; i++) {
-        const size_t dg = db.add_begin();
+        const size_t dg = db.add_begin(true);
         id_round_epoch_origin(v[i].id, v[i].round, v[i].epoch, v[i].origin, db.arena);
         db.add_end();
         if (v[i].epoch != c.epoch) vres[i] = NWV_DAG_INVALID_EPOCH;
@@ -342,11 +374,11 @@ int verify_mixed(nwv_ctx* ctx, const nwv_committee& c, size_t nh, const nwv_head
         }
         HeaderPlan& hp = cplan[i];
         plan_header(c, x.header, db, hp);
-        const size_t cdig = db.add_begin();
+        const size_t cdig = db.add_begin(true);
         id_round_epoch_origin(x.header.id, x.header.round, x.header.epoch, x.header.author, db.arena);
         db.add_end();
         if (hp.pre || hp.post) continue;  // the header's own error decides
-        hp.sig = (long)sb.add(x.header.author, x.header.signature, hp.digest);
+        hp.sig = (long)sb.add_header(x.header.author, x.header.signature, hp.digest, x.header.id);
         // bitmap -> pks in committee order, as the filter at :505-520
         uint64_t weight = 0;
         size_t it = 0;

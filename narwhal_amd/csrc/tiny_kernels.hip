@@ -17,6 +17,10 @@
 //            writes the batch verdict and stores both into the lane's polled host word
 // Against the batch MSM path for these sizes (five launches: prep, sort, bucket, tail's 128-
 // doubling row chain), the device time is the R decompression plus ~10 us.
+// k_ed_tiny_fused (opt-in, nwv_set_typed_fused) is the same check for a typed call whose digests
+// ride in the same launch: the hashing lane compresses a vote's / certificate's one-block preimage
+// itself, and workgroups behind the signatures' hash the header preimages for the host.
+#include "comb.h"
 #include "msm.h"
 
 using namespace nwv;
@@ -71,13 +75,18 @@ static constexpr int TINY_WAVES = 2;
     do {                                                                                        \
         if (a.stamps && blockIdx.x == 0 && lane == 0) a.stamps[k] = __builtin_amdgcn_s_memrealtime(); \
     } while (0)
-extern "C" __global__ void __launch_bounds__(64 * TINY_WAVES) k_ed_tiny(TinyArgs a) {
+// FUSED (k_ed_tiny_fused, a typed call with the setting nwv_set_typed_fused): signature i's message
+// is what typed_message (comb.h) makes of f.src[i] -- the literal, or the digest of a one-block
+// preimage that the hashing lane compresses first.  The unfused instantiation is k_ed_tiny as it was.
+template <bool FUSED>
+__device__ __forceinline__ void ed_tiny_block(const TinyArgs& a, const TypedFusedArgs& f) {
 #if defined(__HIP_DEVICE_COMPILE__)
     __shared__ uint32_t rsh[4 * 48];     // wave 0's rows (48 words each; row 0 is R)
     __shared__ uint32_t rrec[32];        // [8] R: X | Y | Z (10 limbs each); word 31: 1 = R does not decode
     __shared__ int dg[2][COMB_TABLES];   // digits of s and of k
     __shared__ uint32_t hok;             // s < l
     __shared__ uint32_t pts[64 * P3_WORDS];  // the 64 comb terms, summed in place
+    __shared__ uint32_t dmsg[FUSED ? TYPED_DBUF_WORDS : 1];  // FUSED: the digest the signature is over
     const int t = threadIdx.x, wv = t >> 6, lane = t & 63;
     const uint32_t i = blockIdx.x;       // this workgroup's signature (grid = n)
     if (wv == 0) {
@@ -111,7 +120,10 @@ extern "C" __global__ void __launch_bounds__(64 * TINY_WAVES) k_ed_tiny(TinyArgs
             msm_load8(a.pk + 32 * (size_t)i, Aw);
             msm_load8(a.sig + 64 * (size_t)i, Rw);
             msm_load8(a.sig + 64 * (size_t)i + 32, Sw);
-            const bool sok = lane_hash(Aw, Rw, Sw, a.msg + a.off[i], a.len[i], k) == FLAG_S_OK;
+            const uint8_t* mp = a.msg + a.off[i];
+            uint32_t ml = a.len[i];
+            if (FUSED) mp = typed_message(f.src[i], mp, ml, dmsg, f.short_out);  // (dmsg: this lane's alone)
+            const bool sok = lane_hash(Aw, Rw, Sw, mp, ml, k) == FLAG_S_OK;
             hok = sok ? 1u : 0u;
             if (!sok) {  // s >= l fails the signature; its digits would index past the tables
 #pragma unroll
@@ -176,7 +188,8 @@ extern "C" __global__ void __launch_bounds__(64 * TINY_WAVES) k_ed_tiny(TinyArgs
             if (ok) atomicOr(acc, 1ull << i);
             __threadfence();
             const uint32_t arrived = atomicAdd(a.ws + 2, 1u);
-            if (arrived == gridDim.x - 1) {  // the last workgroup: every verdict bit is in
+            // (FUSED: the grid also holds the digest workgroups, which do not arrive here)
+            if (arrived == (FUSED ? a.n : gridDim.x) - 1) {  // the last workgroup: every verdict bit is in
                 __threadfence();
                 const unsigned long long bits = atomicExch(acc, 0ull);
                 a.ws[2] = 0u;
@@ -195,6 +208,21 @@ extern "C" __global__ void __launch_bounds__(64 * TINY_WAVES) k_ed_tiny(TinyArgs
         }
     }
 #endif
+}
+
+extern "C" __global__ void __launch_bounds__(64 * TINY_WAVES) k_ed_tiny(TinyArgs a) {
+    ed_tiny_block<false>(a, TypedFusedArgs{});
+}
+// A typed call in one launch: workgroups [0, f.sig_blocks) are k_ed_tiny's, one signature each,
+// over typed messages; the workgroups behind them hash the call's side preimages (the header
+// preimages, which only the host's id comparison reads) with the quad form of k_blake2b_quad into
+// pinned host memory.  The two kinds share nothing: no workgroup waits for another.
+extern "C" __global__ void __launch_bounds__(64 * TINY_WAVES) k_ed_tiny_fused(TinyArgs a, TypedFusedArgs f, B2SideArgs s) {
+    if (blockIdx.x >= f.sig_blocks) {
+        b2_side_block(s, blockIdx.x - f.sig_blocks);
+        return;
+    }
+    ed_tiny_block<true>(a, f);
 }
 
 // Per-key comb tables of newly registered keys: lane e of key q = entry e of its table, i 16^j A

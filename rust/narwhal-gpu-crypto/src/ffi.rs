@@ -192,6 +192,11 @@ extern "C" {
     pub fn nwv_set_comb_pass_max(ctx: *mut NwvCtx, n: usize) -> c_int;
     pub fn nwv_comb_pass_max(ctx: *const NwvCtx) -> usize;
     pub fn nwv_diag_comb_pass(ctx: *const NwvCtx, out: *mut u64) -> c_int;
+    // typed calls in one launch (opt-in, default off); diagnostics out[3]: fused tiny launches,
+    // fused comb launches, calls that asked for the path and took the two-launch form
+    pub fn nwv_set_typed_fused(ctx: *mut NwvCtx, on: c_int) -> c_int;
+    pub fn nwv_typed_fused(ctx: *const NwvCtx) -> c_int;
+    pub fn nwv_diag_typed_fused(ctx: *const NwvCtx, out: *mut u64) -> c_int;
     pub fn nwv_device_ordinal(ctx: *const NwvCtx, i: c_int) -> c_int;
     pub fn nwv_diag_device_counters(
         ctx: *mut NwvCtx,
@@ -271,6 +276,27 @@ extern "C" {
         key_idx: *const u32,
         sig: *const u8,
         digest_idx: *const u32,
+        seed32: *const u8,
+        all_valid: *mut c_int,
+        verdict_bits_or_null: *mut u64,
+    ) -> c_int;
+    // message m < n_pre: the digest of preimage m; n_pre + k: literal k of lits (32 bytes each)
+    pub fn nwv_ed25519_verify_batch_typed(
+        ctx: *mut NwvCtx,
+        n_pre: usize,
+        pre_base: *const u8,
+        pre_off: *const u64,
+        pre_len: *const u64,
+        pre_short: *const u8,
+        digests_out: *mut u8,
+        n_lit: usize,
+        lits: *const u8,
+        n_keys: usize,
+        keys: *const u8,
+        n: usize,
+        key_idx: *const u32,
+        sig: *const u8,
+        msg_idx: *const u32,
         seed32: *const u8,
         all_valid: *mut c_int,
         verdict_bits_or_null: *mut u64,

@@ -456,6 +456,24 @@ pub fn latency_max() -> usize {
     unsafe { ffi::nwv_latency_max(ctx(), ffi::NWV_ENGINE_ED25519) }
 }
 
+/// Typed calls in one launch (`nwv_set_typed_fused`, opt-in): with `on`, a Header / Vote /
+/// Certificate verification by registered committee keys runs its digests and its signatures in a
+/// single kernel launch when it qualifies; every other call, and every call with it off (the
+/// default), takes the launches it takes today.  Results are identical in both forms.
+pub fn typed_fused_set(on: bool) -> Result<(), String> {
+    let rc = unsafe { ffi::nwv_set_typed_fused(ctx(), if on { 1 } else { 0 }) };
+    if rc == ffi::NWV_OK {
+        Ok(())
+    } else {
+        Err(last_error())
+    }
+}
+
+/// Whether `typed_fused_set` is on.
+pub fn typed_fused() -> bool {
+    unsafe { ffi::nwv_typed_fused(ctx()) != 0 }
+}
+
 /// Lane counters of one device object of an engine (`ffi::NWV_ENGINE_*`): latency-class calls, those
 /// on a reserved lane, those that waited; other calls, those that waited; reserved lanes open, the
 /// reserved-lane cap, ordinary lanes open.

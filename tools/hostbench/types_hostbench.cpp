@@ -34,6 +34,14 @@ extern "C" int nwv_ed25519_verify_batch_keyed_digests(nwv_ctx* ctx, size_t n_pre
     if (bits) std::memset(bits, 0xff, 8 * ((n + 63) / 64));
     return NWV_OK;
 }
+// (the typed form is off in the stubbed engine: the types layer then builds the call above)
+extern "C" int nwv_typed_fused(const nwv_ctx*) { return 0; }
+extern "C" int nwv_ed25519_verify_batch_typed(nwv_ctx*, size_t, const uint8_t*, const uint64_t*, const uint64_t*,
+                                              const uint8_t*, uint8_t*, size_t, const uint8_t*, size_t, const uint8_t*,
+                                              size_t, const uint32_t*, const uint8_t*, const uint32_t*, const uint8_t*,
+                                              int*, uint64_t*) {
+    return NWV_ERR_ARG;
+}
 
 // the BLS12-381 layer's engine calls (nwv_types.cpp links them; this bench times the Ed25519 path)
 extern "C" int nwv_bls_keycache_register(nwv_ctx*, size_t, const uint8_t*) { return NWV_OK; }
