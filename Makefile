@@ -48,7 +48,8 @@ hostemu: tests/_build/libhostemu.so tests/_build/libsvcstub.so tests/_build/libb
 	tests/_build/libblsapkring.so tests/_build/libblsaremu.so tests/_build/libblskeybatch.so \
 	tests/_build/libblskbemu.so tests/_build/libblsademu.so tests/_build/libblswvemu.so \
 	tests/_build/libcombpassemu.so tests/_build/libtypedfusedemu.so \
-	tests/_build/libtailrcemu.so tests/_build/liblanepool.so tests/_build/libdstream.so
+	tests/_build/libtailrcemu.so tests/_build/liblanepool.so tests/_build/libdstream.so \
+	tests/_build/libedplan.so
 # the digest stream (digest_stream.h: chunk pool, hold-back rule, tick plan, pump, callbacks) over a stub
 # device that runs the work records with blake2b.h's compression (tests/test_digest_stream_host.py)
 tests/_build/libdstream.so: tests/hostemu/digest_stream_stub.cpp narwhal_amd/csrc/digest_stream.h \
@@ -104,6 +105,10 @@ tests/_build/libkcalloc.so: tests/hostemu/keycache_alloc_stub.cpp narwhal_amd/cs
 tests/_build/libplace.so: tests/hostemu/place_stub.cpp narwhal_amd/csrc/place.h
 	@mkdir -p tests/_build
 	g++ -O1 -g -std=c++17 -fPIC -shared -pthread -o $@ tests/hostemu/place_stub.cpp
+# the Ed25519 path choice (ed_plan.h) with no HIP (tests/test_ed_plan_host.py)
+tests/_build/libedplan.so: tests/hostemu/ed_plan_stub.cpp narwhal_amd/csrc/ed_plan.h include/nwv.h
+	@mkdir -p tests/_build
+	g++ -O1 -g -std=c++17 -fPIC -shared -o $@ tests/hostemu/ed_plan_stub.cpp
 # the lane pools' lease rule (lane_pool.h) with no HIP (tests/test_lane_pool_host.py)
 tests/_build/liblanepool.so: tests/hostemu/lane_pool_stub.cpp narwhal_amd/csrc/lane_pool.h
 	@mkdir -p tests/_build

@@ -29,6 +29,7 @@
 #include "comb_kernels.hip"
 #include "each_kernels.hip"
 #include "digest_stream.h"
+#include "ed_plan.h"
 #include "group_keys.h"
 #include "keycache_alloc.h"
 #include "lane_pool.h"
@@ -158,17 +159,11 @@ struct EdBuffers {
     bool kc_split = false;      // keyed batch whose keys are all in the device's key cache
     // the last batch MSM already built the per-signature fallback's tables (early form, msm_launch)
     bool tables_ready = false;
-    // a keyed batch of at most TINY_MAX signatures by registered keys (ed_stage_keyed): the
-    // one-launch path (k_ed_tiny) with each signature's key cache slot and comb table
-    bool tiny = false;
+    nwv::EdPlan plan;  // the staged batch's path (ed_plan.h): keyed staging sets it, else the default one
+    // plan Tiny: each signature's key cache slot and comb table, for k_ed_tiny's arguments
     uint32_t tiny_slot[TINY_MAX], tiny_cidx[TINY_MAX];
-    // a keyed batch above TINY_MAX by registered keys that takes k_ed_comb (ed_stage_keyed): each
-    // signature's key cache slot and comb table, staged with the batch (views into the arena)
-    bool comb = false;
+    // plan Comb or comb_pass: the same for k_ed_comb / k_ed_comb_pass, staged with the batch (views)
     DevBuf comb_slot, comb_cidx;
-    // the same arrays staged for the per-signature pass alone (ed_stage_keyed, nwv_set_comb_pass_max):
-    // the batch takes the MSM, and k_ed_comb_pass names the bad set if the MSM does not accept
-    bool comb_pass = false;
     void release() {
         for (DevBuf* b : {&pk, &sig, &msg, &off, &len, &kbuf, &flags, &tables, &verdict, &m_scal,
                           &m_partial, &m_state, &m_pts, &m_digits, &m_cnt, &m_tiles, &m_entries,
@@ -178,9 +173,7 @@ struct EdBuffers {
         nkeys_distinct = 0;
         kc_split = false;
         tables_ready = false;
-        tiny = false;
-        comb = false;
-        comb_pass = false;
+        plan = nwv::EdPlan{};
     }
 };
 
@@ -296,6 +289,38 @@ int with_device(Lane& d) {
     NWV_HIP(hipSetDevice(d.ordinal));
     return NWV_OK;
 }
+
+// the staged inputs and the device's key tables into a kernel's argument struct (any with these members)
+template <class Args>
+void set_inputs(Args& a, const EdBuffers& b) {
+    a.pk = b.pk.as<uint8_t>();
+    a.sig = b.sig.as<uint8_t>();
+    a.msg = b.msg.as<uint8_t>();
+    a.off = b.off.as<uint64_t>();
+    a.len = b.len.as<uint32_t>();
+}
+template <class Args>
+void set_key_tables(Args& a, const Lane& d) {
+    a.kc = d.gpu->kc.recs.as<uint32_t>();
+    a.combs = d.gpu->kc.combs.as<uint32_t>();
+    a.bcomb = d.gpu->comb.as<uint32_t>();
+}
+
+// Batches of at least this many signatures go through the MSM (K5); smaller ones through the
+// per-signature pipeline (tools/latency_sweep.py measures the crossover: the MSM's quad-lane
+// window Horner is shorter than the per-signature Straus chain already at small n).
+#ifndef NWV_MSM_MIN_N_DEFAULT
+#define NWV_MSM_MIN_N_DEFAULT 1
+#endif
+size_t msm_min_n() {
+    static const size_t v = [] {
+        const char* e = std::getenv("NWV_MSM_MIN_N");
+        return e ? (size_t)std::strtoull(e, nullptr, 10) : (size_t)NWV_MSM_MIN_N_DEFAULT;
+    }();
+    return v;
+}
+
+using nwv::EdPath;
 
 // The hold of a call on its device's key cache.  Every call that obtains slot or table indices
 // takes it shared before it looks them up and keeps it until its kernels have finished on the
@@ -498,9 +523,8 @@ int ed_scratch(EdBuffers& b, size_t n) {
 //   - a context with NWV_FLAG_NO_EACH_ROW or NWV_FLAG_MSM_ALWAYS.
 // (The caller counts the pass in the device's n_each, whichever kernels run it.)
 enum EdCaller { ED_CALL, ED_STAGED };
-int ed_launch(Lane& d, EdBuffers& b, size_t n, hipStream_t stream, hipEvent_t* ev,
-              const uint32_t* msm_pts = nullptr, bool tables_ready = false, const uint32_t* gate = nullptr,
-              EdCaller who = ED_CALL) {
+int ed_launch(Lane& d, EdBuffers& b, size_t n, hipStream_t stream, hipEvent_t* ev, const uint32_t* msm_pts,
+              bool tables_ready, const uint32_t* gate, EdCaller who) {
     if (n == 0) return NWV_OK;
     if (who == ED_CALL && !tables_ready && !gate && !ev && d.gpu && n <= d.gpu->each_row_max.load() &&
         !(d.flags & (NWV_FLAG_NO_EACH_ROW | NWV_FLAG_MSM_ALWAYS))) {
@@ -509,11 +533,7 @@ int ed_launch(Lane& d, EdBuffers& b, size_t n, hipStream_t stream, hipEvent_t* e
         if (rc) return rc;
         NWV_HIP(hipMemsetAsync(b.verdict.p, 0, 8 * words, stream));
         EachArgs a{};
-        a.pk = b.pk.as<uint8_t>();
-        a.sig = b.sig.as<uint8_t>();
-        a.msg = b.msg.as<uint8_t>();
-        a.off = b.off.as<uint64_t>();
-        a.len = b.len.as<uint32_t>();
+        set_inputs(a, b);
         a.bcomb = d.gpu->comb.as<uint32_t>();
         a.verdict = b.verdict.as<unsigned long long>();
         if (msm_pts) {  // (msm_reusable: k_msm_prep stored k and the flags with the records)
@@ -1061,31 +1081,43 @@ struct KeyedTail {
     const uint32_t* koff;  // m + 1
     const uint32_t* ksig;  // n
     const uint32_t* kslot;  // m key cache slots, or null (uncached)
-    // k_ed_comb's per-signature tables (n key cache slots, n comb table indices), or null
+    // k_ed_comb's / k_ed_comb_pass's per-signature tables (n slots, n comb table indices), or null
     const uint32_t* sig_slot = nullptr;
     const uint32_t* sig_cidx = nullptr;
-    bool pass_only = false;  // the tables are for k_ed_comb_pass behind the MSM, not for k_ed_comb
+};
+// The caller's arrays of a batch and the range [lo, hi) of them to stage
+struct EdBatch {
+    const uint8_t *sig, *msg_base;
+    const uint64_t* msg_off;
+    const uint32_t* msg_len;
+    size_t lo, hi;
+};
+// What a staging may be told besides (ed_stage reads the first two, ed_stage_keyed all of them)
+struct StageOpts {
+    const DevBuf* dev_msg = nullptr;  // the messages are already on the device (offsets index it as they are)
+    size_t msg_span = 0;  // the first msg_span bytes of msg_base go as they are (a typed call's arena)
+    bool kc_lookup_only = false;  // keycache_slots' lookup_only
+    size_t comb_max = 0;          // the comb path's limit for this call (0: not offered)
+    std::vector<uint32_t>* pin_out = nullptr;  // a staged batch: its key cache slots, pinned
 };
 
-int ed_stage(Lane& d, EdBuffers& b, size_t lo, size_t hi, const uint8_t* pk, const uint8_t* sig,
-             const uint8_t* msg_base, const uint64_t* msg_off, const uint32_t* msg_len,
-             const uint8_t* seed32, const KeyedTail* kt = nullptr, const DevBuf* dev_msg = nullptr,
-             size_t msg_span = 0) {
-    const size_t n = hi - lo;
+// pk: one key a signature, indexed as the batch's arrays are; kt: a keyed batch's tables, or null
+int ed_stage(Lane& d, EdBuffers& b, const EdBatch& in, const uint8_t* pk, const uint8_t* seed32,
+             const KeyedTail* kt, const StageOpts& opt) {
+    const auto [sig, msg_base, msg_off, msg_len, lo, hi] = in;
+    const DevBuf* const dev_msg = opt.dev_msg;
+    const size_t n = hi - lo, msg_span = opt.msg_span;
     uint64_t mlo = UINT64_MAX, mhi = 0;
     for (size_t i = lo; i < hi; i++) {
         mlo = std::min<uint64_t>(mlo, msg_off[i]);
         mhi = std::max<uint64_t>(mhi, msg_off[i] + msg_len[i]);
     }
     if (n == 0 || mhi < mlo) { mlo = 0; mhi = 0; }
-    // msg_span: the first msg_span bytes of msg_base go as they are (a typed call's arena holds
-    // tables behind the messages, at offsets the kernels are given)
     if (msg_span) {
         if (mhi > msg_span) return set_err(NWV_ERR_ARG, "message past the arena span");
         mlo = 0;
         mhi = msg_span;
     }
-    // dev_msg: the messages are already on the device (offsets index it as they are)
     if (dev_msg) {
         if (mhi + MSG_PAD > dev_msg->cap) return set_err(NWV_ERR_ARG, "device message offset out of range");
         mlo = 0;
@@ -1100,10 +1132,10 @@ int ed_stage(Lane& d, EdBuffers& b, size_t lo, size_t hi, const uint8_t* pk, con
     const size_t m = kt ? kt->m : 0;
     const size_t o_koff = o_keys + (kt ? up(32 * m + 32) : 0), o_ksig = o_koff + (kt ? up(4 * m + 8) : 0);
     const size_t o_kslot = o_ksig + (kt ? up(4 * n + 8) : 0);
-    const bool comb = kt && kt->sig_slot && kt->sig_cidx;
+    const bool tabs = kt && kt->sig_slot && kt->sig_cidx;
     const size_t o_cslot = o_kslot + (kt && kt->kslot ? up(4 * m + 8) : 0);
-    const size_t o_ccidx = o_cslot + (comb ? up(4 * n + 8) : 0);
-    const size_t total = o_ccidx + (comb ? up(4 * n + 8) : 0);
+    const size_t o_ccidx = o_cslot + (tabs ? up(4 * n + 8) : 0);
+    const size_t total = o_ccidx + (tabs ? up(4 * n + 8) : 0);
     int rc;
     if ((rc = b.in.ensure(total))) return rc;
     // views into the arena are stale once it may have moved: drop the ones not re-pointed below
@@ -1114,7 +1146,7 @@ int ed_stage(Lane& d, EdBuffers& b, size_t lo, size_t hi, const uint8_t* pk, con
         for (DevBuf* v : {&b.keys, &b.koff, &b.ksig})
             if (v->view) v->release();
     if ((!kt || !kt->kslot) && b.kslot.view) b.kslot.release();
-    if (!comb)
+    if (!tabs)
         for (DevBuf* v : {&b.comb_slot, &b.comb_cidx})
             if (v->view) v->release();
     if (!inputs && ((rc = b.pk.ensure(32 * n + 16)) || (rc = b.sig.ensure(64 * n + 16)))) return rc;
@@ -1125,9 +1157,6 @@ int ed_stage(Lane& d, EdBuffers& b, size_t lo, size_t hi, const uint8_t* pk, con
     uint8_t* h = static_cast<uint8_t*>(d.hstage.p);
     d.pksig_pending = false;
     b.tables_ready = false;
-    b.tiny = false;
-    b.comb = false;
-    b.comb_pass = false;
     // large stagings: the caller's pk / sig / message bytes are packed piece by piece with each
     // piece's DMA queued at once (pack_copy_h2d); the small computed regions go first
     const bool piped = 96 * (inputs ? n : 0) + mbytes >= ((size_t)16 << 20);
@@ -1147,7 +1176,7 @@ int ed_stage(Lane& d, EdBuffers& b, size_t lo, size_t hi, const uint8_t* pk, con
         std::memcpy(h + o_koff, kt->koff, 4 * (m + 1));
         if (n) std::memcpy(h + o_ksig, kt->ksig, 4 * n);
         if (kt->kslot) std::memcpy(h + o_kslot, kt->kslot, 4 * m);
-        if (comb) {
+        if (tabs) {
             std::memcpy(h + o_cslot, kt->sig_slot, 4 * n);
             std::memcpy(h + o_ccidx, kt->sig_cidx, 4 * n);
         }
@@ -1200,15 +1229,15 @@ int ed_stage(Lane& d, EdBuffers& b, size_t lo, size_t hi, const uint8_t* pk, con
         b.koff.set_view(g + o_koff, 4 * m + 8);
         b.ksig.set_view(g + o_ksig, 4 * n + 8);
         if (kt->kslot) b.kslot.set_view(g + o_kslot, 4 * m + 8);
-        if (comb) {
+        if (tabs) {
             b.comb_slot.set_view(g + o_cslot, 4 * n + 8);
             b.comb_cidx.set_view(g + o_ccidx, 4 * n + 8);
         }
     }
     b.nkeys_distinct = m;
     b.kc_split = kt && kt->kslot && m;
-    b.comb = comb && !kt->pass_only;
-    b.comb_pass = comb && kt->pass_only;
+    // (the default plan, by the flags and msm_min: keyed staging sets its own after this returns)
+    b.plan = nwv::ed_plan(n, d.flags, false, false, false, nwv::EdLimits{0, 0, 0, msm_min_n()});
     return NWV_OK;
 }
 
@@ -1218,7 +1247,7 @@ int ed_stage(Lane& d, EdBuffers& b, size_t lo, size_t hi, const uint8_t* pk, con
 // per key for nothing).  lookup_only: use the cache only if every key is already in it (single
 // verifies: a one-off or undecodable key must neither take a slot for good nor make the call
 // wait for a fill under the device-wide lock).
-int keycache_slots(Lane& d, const uint8_t* keys, size_t m, std::vector<uint32_t>& out, bool lookup_only = false) {
+int keycache_slots(Lane& d, const uint8_t* keys, size_t m, std::vector<uint32_t>& out, bool lookup_only) {
     out.clear();
     static const long max_keys = [] {
         const char* e = std::getenv("NWV_KEYCACHE_MAX_KEYS");
@@ -1350,12 +1379,9 @@ void kc_unpin(KeyCache& kc, std::vector<uint32_t>& slots) {
 // Keyed staging: signature i of [lo, hi) is by keys[key_idx[i]].  The distinct keys that occur
 // in the range are renumbered densely, uploaded with the CSR of signatures per key, and pk is
 // expanded per signature (the per-signature fallback reads it).
-int ed_stage_keyed(Lane& d, EdBuffers& b, size_t lo, size_t hi, size_t n_keys, const uint8_t* keys,
-                   const uint32_t* key_idx, const uint8_t* sig, const uint8_t* msg_base,
-                   const uint64_t* msg_off, const uint32_t* msg_len, const uint8_t* seed32,
-                   const DevBuf* dev_msg = nullptr, bool kc_lookup_only = false, size_t comb_max = 0,
-                   std::vector<uint32_t>* pin_out = nullptr, size_t msg_span = 0) {
-    const size_t n = hi - lo;
+int ed_stage_keyed(Lane& d, EdBuffers& b, const EdBatch& in, size_t n_keys, const uint8_t* keys,
+                   const uint32_t* key_idx, const uint8_t* seed32, const StageOpts& opt) {
+    const size_t lo = in.lo, n = in.hi - lo;
     // per-thread scratch reused across calls (fresh large vectors are page-faulted in every call)
     thread_local std::vector<uint32_t> local, cnt, kid, koff, ksig, cur;
     thread_local std::vector<uint8_t> klist, pk;
@@ -1383,28 +1409,26 @@ int ed_stage_keyed(Lane& d, EdBuffers& b, size_t lo, size_t hi, size_t n_keys, c
     cur.assign(koff.begin(), koff.end() - 1);
     for (size_t i = 0; i < n; i++) ksig[cur[kid[i]]++] = (uint32_t)i;
     thread_local std::vector<uint32_t> kslot;
-    int rc = keycache_slots(d, klist.data(), m, kslot, kc_lookup_only);
+    int rc = keycache_slots(d, klist.data(), m, kslot, opt.kc_lookup_only);
     if (rc) return rc;
-    if (pin_out && !kslot.empty()) {
+    const bool staged = opt.pin_out != nullptr;
+    if (staged && !kslot.empty()) {
         // a staged batch reads these slots on every replay: pinned (under the call's hold, so no
         // retain runs in between) until kc_unpin at nwv_staged_free
         KeyCache& kc = d.gpu->kc;
         std::lock_guard<std::mutex> g(kc.mu);
         for (uint32_t sl : kslot) kc.alloc.pin(sl);
-        *pin_out = kslot;
+        *opt.pin_out = kslot;
     }
-    KeyedTail kt{klist.data(), m, koff.data(), ksig.data(), kslot.empty() ? nullptr : kslot.data()};
-    // the comb path (k_ed_comb): above TINY_MAX and at most comb_max signatures (0: the caller does
-    // not offer it), every key registered (comb table present), no flag that forces a path.  A
-    // batch past comb_max of at most comb_pass_max signatures (0: off; never a staged batch's)
-    // stages the same tables under the same conditions for k_ed_comb_pass behind its MSM.
+    // the batch's path (ed_plan.h).  Where a rule for k_ed_tiny, k_ed_comb or k_ed_comb_pass holds but
+    // for the tables, each signature's slot and comb table are looked up: every key must have one
+    const nwv::EdLimits lim{(size_t)TINY_MAX, opt.comb_max, d.gpu->comb_pass_max.load(), msm_min_n()};
     thread_local std::vector<uint32_t> sig_slot, sig_cidx;
-    const size_t pass_max = pin_out ? 0 : d.gpu->comb_pass_max.load();
-    if (n > (size_t)TINY_MAX && (n <= comb_max || n <= pass_max) && !kslot.empty() &&
-        !(d.flags & (NWV_FLAG_NO_TINY | NWV_FLAG_MSM_ALWAYS | NWV_FLAG_MSM_NEVER))) {
+    bool all = false;
+    if (nwv::ed_plan_wants_tables(n, d.flags, !kslot.empty(), staged, lim)) {
         KeyCache& kc = d.gpu->kc;
         std::lock_guard<std::mutex> g(kc.mu);
-        bool all = kc.comb_cap != 0;
+        all = kc.comb_cap != 0;
         sig_slot.resize(n);
         sig_cidx.resize(n);
         for (size_t i = 0; i < n && all; i++) {
@@ -1414,29 +1438,26 @@ int ed_stage_keyed(Lane& d, EdBuffers& b, size_t lo, size_t hi, size_t n_keys, c
             sig_slot[i] = sl;
             sig_cidx[i] = c;
         }
-        if (all) {
-            kt.sig_slot = sig_slot.data();
-            kt.sig_cidx = sig_cidx.data();
-            kt.pass_only = n > comb_max;
-        }
     }
-    rc = ed_stage(d, b, 0, n, pk.data(), sig + 64 * lo, msg_base, msg_off + lo, msg_len + lo, seed32, &kt, dev_msg,
-                  msg_span);
+    const nwv::EdPlan plan = nwv::ed_plan(n, d.flags, !kslot.empty(), all, staged, lim);
+    const auto [path, comb_pass] = plan;
+    const bool tabs = path == EdPath::Comb || comb_pass;  // the two arrays go to the device with the batch
+    const KeyedTail kt{klist.data(), m, koff.data(), ksig.data(), kslot.empty() ? nullptr : kslot.data(),
+                       tabs ? sig_slot.data() : nullptr, tabs ? sig_cidx.data() : nullptr};
+    rc = ed_stage(d, b, EdBatch{in.sig + 64 * lo, in.msg_base, in.msg_off + lo, in.msg_len + lo, 0, n}, pk.data(), seed32,
+                  &kt, opt);
     if (rc) return rc;
-    // the one-launch path: few signatures, every key registered (comb table present)
-    if (n && n <= (size_t)TINY_MAX && !kslot.empty() && !(d.flags & (NWV_FLAG_NO_TINY | NWV_FLAG_MSM_NEVER))) {
-        KeyCache& kc = d.gpu->kc;
-        std::lock_guard<std::mutex> g(kc.mu);
-        bool all = kc.comb_cap != 0;
-        for (size_t i = 0; i < n && all; i++) {
-            const uint32_t sl = kslot[kid[i]];
-            const uint32_t c = kc.alloc.table_of(sl);
-            all = c != UINT32_MAX;
-            b.tiny_slot[i] = sl;
-            b.tiny_cidx[i] = c;
-        }
-        b.tiny = all;
+    if (path == EdPath::Tiny) {  // they go in k_ed_tiny's arguments
+        std::memcpy(b.tiny_slot, sig_slot.data(), 4 * n);
+        std::memcpy(b.tiny_cidx, sig_cidx.data(), 4 * n);
     }
+    b.plan = plan;
+    return NWV_OK;
+}
+// a message with bytes needs a base to be read from
+int check_msg_base(size_t n, const uint8_t* msg_base, const uint32_t* msg_len) {
+    for (size_t i = 0; i < n && !msg_base; i++)
+        if (msg_len[i]) return set_err(NWV_ERR_ARG, "null msg_base");
     return NWV_OK;
 }
 
@@ -1842,33 +1863,18 @@ int nwv_ed25519_verify_each(nwv_ctx* ctx, size_t n, const uint8_t* pk, const uin
     if (!ctx || (n && (!pk || !sig || !msg_off || !msg_len || !verdict_bits)))
         return set_err(NWV_ERR_ARG, "null argument");
     if (n == 0) return NWV_OK;
-    for (size_t i = 0; i < n; i++)
-        if (msg_len[i] && !msg_base) return set_err(NWV_ERR_ARG, "null msg_base");
+    if (int rc = check_msg_base(n, msg_base, msg_len)) return rc;
     return for_shards(ctx, n, [&](Lane& d, size_t lo, size_t hi) -> int {
-        int rc = ed_stage(d, d.ed, lo, hi, pk, sig, msg_base, msg_off, msg_len, nullptr);
+        int rc = ed_stage(d, d.ed, EdBatch{sig, msg_base, msg_off, msg_len, lo, hi}, pk, nullptr, nullptr, StageOpts{});
         if (rc) return rc;
         d.gpu->n_each++;
-        if ((rc = ed_launch(d, d.ed, hi - lo, d.stream, nullptr))) return rc;
+        if ((rc = ed_launch(d, d.ed, hi - lo, d.stream, nullptr, nullptr, false, nullptr, ED_CALL))) return rc;
         const size_t words = (hi - lo + 63) / 64;
         NWV_HIP(hipMemcpyAsync(verdict_bits + lo / 64, d.ed.verdict.p, 8 * words,
                                hipMemcpyDeviceToHost, d.stream));
         NWV_HIP(hipStreamSynchronize(d.stream));
         return NWV_OK;
     });
-}
-
-// Batches of at least this many signatures go through the MSM (K5); smaller ones through the
-// per-signature pipeline (tools/latency_sweep.py measures the crossover: the MSM's quad-lane
-// window Horner is shorter than the per-signature Straus chain already at small n).
-#ifndef NWV_MSM_MIN_N_DEFAULT
-#define NWV_MSM_MIN_N_DEFAULT 1
-#endif
-static size_t msm_min_n() {
-    static const size_t v = [] {
-        const char* e = std::getenv("NWV_MSM_MIN_N");
-        return e ? (size_t)std::strtoull(e, nullptr, 10) : (size_t)NWV_MSM_MIN_N_DEFAULT;
-    }();
-    return v;
 }
 
 // OS entropy for the batch coefficients, as the reference's OsRng / thread_rng: a per-thread
@@ -1927,8 +1933,43 @@ static const uint32_t* msm_reusable(const Lane& d, const EdBuffers& b, bool msm_
     return b.m_pts.as<uint32_t>();
 }
 
-static void set_ones(uint64_t* bits, size_t lo, size_t hi) {
-    for (size_t i = lo; i < hi; i++) bits[i >> 6] |= 1ULL << (i & 63);
+// the verdict words of an accepted batch: n ones
+static void accept_all(uint64_t* bits, size_t n) {
+    std::memset(bits, 0, 8 * ((n + 63) / 64));
+    for (size_t i = 0; i < n; i++) bits[i >> 6] |= 1ULL << (i & 63);
+}
+// each shard gets its own coefficient stream: the call's seed with the shard's start mixed in
+static void shard_seed(const uint8_t seed[32], size_t lo, uint8_t out[32]) {
+    std::memcpy(out, seed, 32);
+    for (int k = 0; k < 8; k++) out[24 + k] ^= (uint8_t)((uint64_t)lo >> (8 * k));
+}
+// The lane's polled host word: a kernel's last workgroup stores (sequence number << 2 | code) there
+// and the host spins on it instead of copying the verdict back (NWV_NO_HOST_POLL: the copy; 1K p50
+// 0.233 -> 0.227 ms).  Only calls on the lane's own stream poll: null for the others.
+static uint32_t* poll_word(const Lane& d, hipStream_t stream) {
+    static const bool no_poll = std::getenv("NWV_NO_HOST_POLL") != nullptr;
+    return (!no_poll && stream == d.stream) ? d.hword : nullptr;
+}
+// the lane's next sequence number (30 bits, never 0), and the word (if any) cleared for it
+static uint32_t poll_arm(Lane& d, uint32_t* hv) {
+    d.hseq = (d.hseq + 1) & 0x3FFFFFFFu;
+    if (d.hseq == 0) d.hseq = 1;
+    if (hv) __atomic_store_n(hv, 0u, __ATOMIC_RELEASE);
+    return d.hseq;
+}
+// Spin until the word carries seq (bounded at ~2 s), then the stream's own completion (it returns at
+// once; without it p99 rose by ~10 us while p50 gained ~2 us).  *code: the word's low two bits, or -1
+// if it never carried seq (the caller then copies its verdict back).
+static int poll_wait(const uint32_t* hv, uint32_t seq, hipStream_t stream, int* code) {
+    uint32_t v = 0;
+    const auto t0 = std::chrono::steady_clock::now();
+    for (uint64_t k = 0; ((v = __atomic_load_n(hv, __ATOMIC_ACQUIRE)) >> 2) != seq; k++) {
+        if ((k & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) break;
+        __builtin_ia32_pause();
+    }
+    NWV_HIP(hipStreamSynchronize(stream));
+    *code = (v >> 2) == seq ? (int)(v & 3u) : -1;
+    return NWV_OK;
 }
 
 // What a typed call in the fused form adds to the launch of k_ed_tiny / k_ed_comb: the signatures'
@@ -1942,36 +1983,24 @@ static unsigned typed_side_blocks(const TypedLaunch& tf) {
     return (unsigned)((tf.s.n + 16 * B2_SIDE_WAVES - 1) / (16 * B2_SIDE_WAVES));
 }
 
-// k_ed_tiny over a staged tiny keyed batch (b.tiny): every signature's verdict in one launch,
+// k_ed_tiny over a staged keyed batch whose plan is Tiny: every signature's verdict in one launch,
 // read back through the lane's polled host word (or the workspace when the lane has none).
-// tf: the call is a typed one in the fused form (k_ed_tiny_fused)
+// tf: the call is a typed one in the fused form (k_ed_tiny_fused), or null
 static int tiny_on_device(Lane& d, EdBuffers& b, size_t n, hipStream_t stream, int* ok, uint64_t* bits,
-                          const TypedLaunch* tf = nullptr) {
+                          const TypedLaunch* tf) {
     int rc;
     if (!d.tiny_ws.p) {
         if ((rc = d.tiny_ws.ensure(64))) return rc;
         NWV_HIP(hipMemsetAsync(d.tiny_ws.p, 0, 64, stream));
     }
-    static const bool no_poll = std::getenv("NWV_NO_HOST_POLL") != nullptr;
-    uint32_t* hv = (!no_poll && stream == d.stream) ? d.hword : nullptr;
+    uint32_t* hv = poll_word(d, stream);
     TinyArgs a{};
-    a.pk = b.pk.as<uint8_t>();
-    a.sig = b.sig.as<uint8_t>();
-    a.msg = b.msg.as<uint8_t>();
-    a.off = b.off.as<uint64_t>();
-    a.len = b.len.as<uint32_t>();
-    a.kc = d.gpu->kc.recs.as<uint32_t>();
-    a.combs = d.gpu->kc.combs.as<uint32_t>();
-    a.bcomb = d.gpu->comb.as<uint32_t>();
+    set_inputs(a, b);
+    set_key_tables(a, d);
     a.ws = d.tiny_ws.as<uint32_t>();
     a.hword = hv;
     a.n = (uint32_t)n;
-    if (hv) {
-        d.hseq = (d.hseq + 1) & 0x3FFFFFFFu;
-        if (d.hseq == 0) d.hseq = 1;
-        a.hseq = d.hseq;
-        __atomic_store_n(hv, 0u, __ATOMIC_RELEASE);
-    }
+    if (hv) a.hseq = poll_arm(d, hv);  // (a sequence number only when the word is polled)
     std::memcpy(a.kslot, b.tiny_slot, 4 * n);
     std::memcpy(a.cidx, b.tiny_cidx, 4 * n);
     static const bool stamps = std::getenv("NWV_TINY_STAMPS") != nullptr;  // diagnostics only
@@ -1992,29 +2021,16 @@ static int tiny_on_device(Lane& d, EdBuffers& b, size_t n, hipStream_t stream, i
         (void)hipStreamSynchronize(stream);
         return set_err(NWV_ERR_HIP, "k_ed_tiny launch");
     }
-    uint64_t vb = 0;
-    uint32_t all = 0;
-    bool got = false;
-    if (hv) {
-        uint32_t v = 0;
-        const auto t0 = std::chrono::steady_clock::now();
-        for (uint64_t k = 0; ((v = __atomic_load_n(hv, __ATOMIC_ACQUIRE)) >> 2) != a.hseq; k++) {
-            if ((k & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) break;
-            __builtin_ia32_pause();
-        }
-        NWV_HIP(hipStreamSynchronize(stream));
-        if ((v >> 2) == a.hseq) {
-            vb = (uint64_t)hv[2] | ((uint64_t)hv[3] << 32);
-            all = (v & 3u) == 1u;
-            got = true;
-        }
-    }
-    if (!got) {
-        uint32_t r[4] = {0, 0, 0, 0};
+    uint32_t r[4] = {0, 0, 0, 0};  // the verdict bits (two words), all valid
+    int code = -1;
+    if (hv && (rc = poll_wait(hv, a.hseq, stream, &code))) return rc;
+    if (code >= 0) {
+        r[0] = hv[2];
+        r[1] = hv[3];
+        r[2] = code == 1;
+    } else {
         NWV_HIP(hipMemcpyAsync(r, a.ws + 4, 16, hipMemcpyDeviceToHost, stream));
         NWV_HIP(hipStreamSynchronize(stream));
-        vb = (uint64_t)r[0] | ((uint64_t)r[1] << 32);
-        all = r[2];
     }
     htrace("batch:tiny-done");
     if (stamps) {  // phase times of workgroup 0 in us from its start (s_memrealtime: 100 MHz)
@@ -2024,17 +2040,17 @@ static int tiny_on_device(Lane& d, EdBuffers& b, size_t n, hipStream_t stream, i
                          (t[1] - t[0]) / 100.0, (t[3] - t[0]) / 100.0, (t[2] - t[0]) / 100.0, (t[4] - t[0]) / 100.0,
                          (t[5] - t[0]) / 100.0, (t[6] - t[0]) / 100.0);
     }
-    *ok = all ? 1 : 0;
-    if (bits) bits[0] = vb;
+    *ok = r[2] ? 1 : 0;
+    if (bits) bits[0] = (uint64_t)r[0] | ((uint64_t)r[1] << 32);
     return NWV_OK;
 }
 
-// k_ed_comb over a staged registered-key batch above TINY_MAX (b.comb): every signature's exact
+// k_ed_comb over a staged registered-key batch whose plan is Comb: every signature's exact
 // verdict in one launch.  The batch verdict comes back through the lane's polled host word (or
 // the workspace when the lane has none); the verdict words are copied back only for a rejected
 // batch whose caller asked for them.
 static int comb_on_device(Lane& d, EdBuffers& b, size_t n, hipStream_t stream, int* ok, uint64_t* bits,
-                          const TypedLaunch* tf = nullptr) {
+                          const TypedLaunch* tf) {
     int rc;
     const size_t words = (n + 63) / 64;
     // workspace: 64 bytes (arrivals, batch verdict), the accumulated words, the result words
@@ -2044,17 +2060,10 @@ static int comb_on_device(Lane& d, EdBuffers& b, size_t n, hipStream_t stream, i
         NWV_HIP(hipMemsetAsync(d.comb_ws.p, 0, d.comb_ws.cap, stream));
     }
     const size_t wcap = (d.comb_ws.cap - 64) / 16;
-    static const bool no_poll = std::getenv("NWV_NO_HOST_POLL") != nullptr;
-    uint32_t* hv = (!no_poll && stream == d.stream) ? d.hword : nullptr;
+    uint32_t* hv = poll_word(d, stream);
     CombArgs a{};
-    a.pk = b.pk.as<uint8_t>();
-    a.sig = b.sig.as<uint8_t>();
-    a.msg = b.msg.as<uint8_t>();
-    a.off = b.off.as<uint64_t>();
-    a.len = b.len.as<uint32_t>();
-    a.kc = d.gpu->kc.recs.as<uint32_t>();
-    a.combs = d.gpu->kc.combs.as<uint32_t>();
-    a.bcomb = d.gpu->comb.as<uint32_t>();
+    set_inputs(a, b);
+    set_key_tables(a, d);
     a.kslot = b.comb_slot.as<uint32_t>();
     a.cidx = b.comb_cidx.as<uint32_t>();
     a.ws = d.comb_ws.as<uint32_t>();
@@ -2062,10 +2071,7 @@ static int comb_on_device(Lane& d, EdBuffers& b, size_t n, hipStream_t stream, i
     a.bits = a.acc + wcap;
     a.hword = hv;
     a.n = (uint32_t)n;
-    d.hseq = (d.hseq + 1) & 0x3FFFFFFFu;  // (the workspace's verdict word carries it too)
-    if (d.hseq == 0) d.hseq = 1;
-    a.hseq = d.hseq;
-    if (hv) __atomic_store_n(hv, 0u, __ATOMIC_RELEASE);
+    a.hseq = poll_arm(d, hv);  // (always: the workspace's verdict word carries the number too)
     const unsigned sig_blocks = (unsigned)((n + COMB_G - 1) / COMB_G);
     if (tf) {
         TypedFusedArgs f = tf->f;
@@ -2079,40 +2085,28 @@ static int comb_on_device(Lane& d, EdBuffers& b, size_t n, hipStream_t stream, i
         (void)hipStreamSynchronize(stream);
         return set_err(NWV_ERR_HIP, "k_ed_comb launch");
     }
-    uint32_t code = 0;
-    if (hv) {
-        uint32_t v = 0;
-        const auto t0 = std::chrono::steady_clock::now();
-        for (uint64_t k = 0; ((v = __atomic_load_n(hv, __ATOMIC_ACQUIRE)) >> 2) != a.hseq; k++) {
-            if ((k & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) break;
-            __builtin_ia32_pause();
-        }
-        NWV_HIP(hipStreamSynchronize(stream));
-        if ((v >> 2) == a.hseq) code = v & 3u;
-    }
-    if (code != 1u && code != 2u) {
+    int code = -1;
+    if (hv && (rc = poll_wait(hv, a.hseq, stream, &code))) return rc;
+    if (code != 1 && code != 2) {
         uint32_t r[2] = {0, 0};
         NWV_HIP(hipMemcpyAsync(r, a.ws, 8, hipMemcpyDeviceToHost, stream));
         NWV_HIP(hipStreamSynchronize(stream));
-        code = (r[1] >> 2) == a.hseq ? (r[1] & 3u) : 0u;
-        if (code != 1u && code != 2u) return set_err(NWV_ERR_HIP, "k_ed_comb left no verdict");
+        code = (r[1] >> 2) == a.hseq ? (int)(r[1] & 3u) : 0;
+        if (code != 1 && code != 2) return set_err(NWV_ERR_HIP, "k_ed_comb left no verdict");
     }
     htrace("batch:comb-done");
-    *ok = code == 1u ? 1 : 0;
-    if (bits) {
-        if (*ok) {
-            std::memset(bits, 0, 8 * words);
-            set_ones(bits, 0, n);
-        } else {
-            NWV_HIP(hipMemcpyAsync(bits, a.bits, 8 * words, hipMemcpyDeviceToHost, stream));
-            NWV_HIP(hipStreamSynchronize(stream));
-        }
+    *ok = code == 1 ? 1 : 0;
+    if (bits && *ok) {
+        accept_all(bits, n);
+    } else if (bits) {
+        NWV_HIP(hipMemcpyAsync(bits, a.bits, 8 * words, hipMemcpyDeviceToHost, stream));
+        NWV_HIP(hipStreamSynchronize(stream));
     }
     return NWV_OK;
 }
 
-// k_ed_comb_pass over a registered-key batch staged for it (b.comb_pass): the per-signature pass
-// of a batch whose MSM did not accept, into the verdict words that batch_on_device reads back
+// k_ed_comb_pass over a registered-key batch staged for it (the plan's comb_pass): the per-signature pass
+// of a batch whose MSM did not accept, into the verdict words that each_on_device reads back
 // (zeroed on the stream first, as ed_launch does for the row kernel).  The tables it reads are
 // held by the call's shared hold of the key cache until the lane goes back.  NWV_COMB_PASS_L
 // (4 or 16): lanes a signature; the default is the faster of the two in tools/comb_pass_sweep.py.
@@ -2127,14 +2121,8 @@ static int comb_pass_launch(Lane& d, EdBuffers& b, size_t n, hipStream_t stream)
     if (rc) return rc;
     NWV_HIP(hipMemsetAsync(b.verdict.p, 0, 8 * words, stream));
     CombPassArgs a{};
-    a.pk = b.pk.as<uint8_t>();
-    a.sig = b.sig.as<uint8_t>();
-    a.msg = b.msg.as<uint8_t>();
-    a.off = b.off.as<uint64_t>();
-    a.len = b.len.as<uint32_t>();
-    a.kc = d.gpu->kc.recs.as<uint32_t>();
-    a.combs = d.gpu->kc.combs.as<uint32_t>();
-    a.bcomb = d.gpu->comb.as<uint32_t>();
+    set_inputs(a, b);
+    set_key_tables(a, d);
     a.kslot = b.comb_slot.as<uint32_t>();
     a.cidx = b.comb_cidx.as<uint32_t>();
     a.verdict = b.verdict.as<unsigned long long>();
@@ -2148,125 +2136,104 @@ static int comb_pass_launch(Lane& d, EdBuffers& b, size_t n, hipStream_t stream)
     return NWV_OK;
 }
 
-// Batch verdict of resident buffers: MSM, then (only if it rejects) the per-signature fallback
-// for the exact bad set.  bits: the shard's verdict words (may be null).  A tiny keyed batch by
-// registered keys takes the one-launch per-signature path instead (exact bits, no fallback), and
-// a larger one staged for it (b.comb) the comb path, k_ed_comb.
-static int batch_on_device(Lane& d, EdBuffers& b, size_t n, const uint8_t seed[32], hipStream_t stream,
-                           int* ok, uint64_t* bits, bool state_ready = false) {
-    int rc;
-    if (b.tiny && n <= (size_t)TINY_MAX) {
-        d.gpu->n_tiny++;
-        return tiny_on_device(d, b, n, stream, ok, bits);
-    }
-    if (b.comb && n > (size_t)TINY_MAX) {
-        d.gpu->n_comb++;
-        return comb_on_device(d, b, n, stream, ok, bits);
-    }
-    const bool use_msm = (d.flags & NWV_FLAG_MSM_ALWAYS) ||
-                         (!(d.flags & NWV_FLAG_MSM_NEVER) && n >= msm_min_n());
-    if (use_msm) {
-        d.gpu->n_msm++;
-        htrace("batch:msm-launch");
-        // batch-verdict calls of up to 65,536 signatures (latency-bound: a spinning host thread
-        // costs little) poll the tail's word in pinned host memory instead of copying the verdict
-        // back and waiting for the stream: 1K p50 0.233 -> 0.227 ms (NWV_NO_HOST_POLL: the copy)
-        static const bool no_poll = std::getenv("NWV_NO_HOST_POLL") != nullptr;
-        uint32_t* hv = (!bits && !no_poll && stream == d.stream && n <= 65536) ? d.hword : nullptr;
-        uint32_t seq = 0;
-        if (hv) {
-            d.hseq = (d.hseq + 1) & 0x3FFFFFFFu;
-            if (d.hseq == 0) d.hseq = 1;
-            seq = d.hseq;
-            __atomic_store_n(hv, 0u, __ATOMIC_RELEASE);
-        }
-        if ((rc = msm_launch(d, b, n, seed, stream, nullptr, state_ready, bits != nullptr, hv, seq))) {
-            // a launch that failed part-way may have queued work that still stores into the word:
-            // drain the stream so the lane's next call starts clean
-            (void)hipStreamSynchronize(stream);
-            return rc;
-        }
-        htrace("batch:msm-launched");
-        if (hv) {
-            // spin on the word until it carries this call's sequence number (a few hundred us at
-            // most for the batches that come this way), then the stream's own completion; a word
-            // that never flips (bounded at ~2 s) falls back to the copy below
-            uint32_t v = 0;
-            const auto t0 = std::chrono::steady_clock::now();
-            for (uint64_t k = 0; ((v = __atomic_load_n(hv, __ATOMIC_ACQUIRE)) >> 2) != seq; k++) {
-                if ((k & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) break;
-                __builtin_ia32_pause();
-            }
-            // the stream's own completion too (by now the tail has stored its last word: this
-            // returns at once; without it p99 rose by ~10 us while p50 gained ~2 us)
-            NWV_HIP(hipStreamSynchronize(stream));
-            const uint32_t code = (v >> 2) == seq ? (v & 3u) : 0u;
-            if (code == 1u || code == 2u) {
-                htrace("batch:verdict-polled");
-                *ok = code == 1u ? 1 : 0;
-                return NWV_OK;
-            }
-            // code 3 (the tail could not determine the verdict) or no word: the state copy below
-        }
-        if (bits && b.tables_ready) {
-            // the early form built the fallback's tables: its Straus pass queues behind the MSM now
-            // (gated on the MSM's verdict word) and one read-back brings both
-            if ((rc = ed_launch(d, b, n, stream, nullptr, nullptr, true, b.m_state.as<uint32_t>()))) return rc;
-            uint32_t st[2] = {0, 0};
-            NWV_HIP(hipMemcpyAsync(st, b.m_state.p, 8, hipMemcpyDeviceToHost, stream));
-            NWV_HIP(hipMemcpyAsync(bits, b.verdict.p, 8 * ((n + 63) / 64), hipMemcpyDeviceToHost, stream));
-            NWV_HIP(hipStreamSynchronize(stream));
-            htrace("batch:gated-done");
-            if (st[1] == 1) {
-                std::memset(bits, 0, 8 * ((n + 63) / 64));
-                set_ones(bits, 0, n);
-                *ok = 1;
-            } else {
-                *ok = verdicts_all_valid(bits, n) ? 1 : 0;
-            }
-            return NWV_OK;
-        }
-        uint32_t st[2] = {0, 0};
-        NWV_HIP(hipMemcpyAsync(st, b.m_state.p, 8, hipMemcpyDeviceToHost, stream));
-        NWV_HIP(hipStreamSynchronize(stream));
-        if (st[1] == 1) {
-            *ok = 1;
-            if (bits) {
-                std::memset(bits, 0, 8 * ((n + 63) / 64));
-                set_ones(bits, 0, n);
-            }
-            return NWV_OK;
-        }
-        // a batch of valid signatures always passes (the cofactored equation holds for each term
-        // whatever z_i), so a rejection means some signature is invalid: callers that only want
-        // the batch verdict (fastcrypto's verify_batch / aggregate verify) get it without the
-        // per-signature pass, which only runs to name the bad signatures.  An undetermined MSM
-        // (st[1] == 2: the tail gave up waiting for a window) is never reported as a rejection:
-        // the per-signature pass decides.
-        if (!bits && st[1] == 0) {
-            *ok = 0;
-            return NWV_OK;
-        }
-    }
+// The per-signature pass of a batch on resident buffers, for the exact bad set: k_ed_comb_pass (the
+// key combs instead of a Straus chain a signature) for a batch staged for it, else ed_launch, on the
+// records of the MSM that just ran (msm_ran) where they can be reused.
+static int each_on_device(Lane& d, EdBuffers& b, size_t n, hipStream_t stream, int* ok, uint64_t* bits, bool msm_ran) {
     htrace("batch:fallback");
     d.gpu->n_each++;
-    // a batch staged for it (b.comb_pass: registered keys, under the call's hold of the key cache)
-    // names its bad set from the key combs instead of a Straus chain a signature
-    if (b.comb_pass) {
-        if ((rc = comb_pass_launch(d, b, n, stream))) return rc;
-    } else if ((rc = ed_launch(d, b, n, stream, nullptr, msm_reusable(d, b, use_msm)))) {
-        return rc;
-    }
-    std::vector<uint64_t> tmp;
-    uint64_t* out = bits;
-    if (!out) {
-        tmp.assign((n + 63) / 64, 0);
-        out = tmp.data();
-    }
+    const auto [path, on_combs] = b.plan;
+    const int rc = on_combs ? comb_pass_launch(d, b, n, stream)
+                            : ed_launch(d, b, n, stream, nullptr, msm_reusable(d, b, msm_ran), false, nullptr, ED_CALL);
+    if (rc) return rc;
+    std::vector<uint64_t> tmp(bits ? 0 : (n + 63) / 64);
+    uint64_t* out = bits ? bits : tmp.data();
     NWV_HIP(hipMemcpyAsync(out, b.verdict.p, 8 * ((n + 63) / 64), hipMemcpyDeviceToHost, stream));
     NWV_HIP(hipStreamSynchronize(stream));
     htrace("batch:fallback-done");
     *ok = verdicts_all_valid(out, n) ? 1 : 0;
+    return NWV_OK;
+}
+
+// The batch MSM over resident buffers.  *decided: *ok is the batch's verdict (accepted, or rejected
+// where that is final) and bits, if asked for, are filled (by the gated form when the early form had
+// built the per-signature tables).  Else the per-signature pass decides: the MSM rejected and the bad
+// set is wanted, or it came out undetermined (the tail gave up on a window): never a rejection.
+static int msm_on_device(Lane& d, EdBuffers& b, size_t n, const uint8_t seed[32], hipStream_t stream,
+                         bool state_ready, int* ok, uint64_t* bits, bool* decided) {
+    int rc;
+    *decided = true;
+    d.gpu->n_msm++;
+    htrace("batch:msm-launch");
+    // batch-verdict calls of up to 65,536 signatures (latency-bound: a spinning host thread costs
+    // little) poll the tail's word
+    uint32_t* hv = (!bits && n <= 65536) ? poll_word(d, stream) : nullptr;
+    const uint32_t seq = hv ? poll_arm(d, hv) : 0;
+    if ((rc = msm_launch(d, b, n, seed, stream, nullptr, state_ready, bits != nullptr, hv, seq))) {
+        // a launch that failed part-way may have queued work that still stores into the word:
+        // drain the stream so the lane's next call starts clean
+        (void)hipStreamSynchronize(stream);
+        return rc;
+    }
+    htrace("batch:msm-launched");
+    int code = -1;
+    if (hv && (rc = poll_wait(hv, seq, stream, &code))) return rc;
+    if (code == 1 || code == 2) {
+        htrace("batch:verdict-polled");
+        *ok = code == 1 ? 1 : 0;
+        return NWV_OK;
+    }
+    // code 3 (the tail could not determine the verdict), no word or no poll: the state copy
+    uint32_t st[2] = {0, 0};
+    const bool gated = bits && b.tables_ready;
+    // the early form built the fallback's tables: its Straus pass queues behind the MSM now (gated
+    // on the MSM's verdict word) and one read-back brings both
+    if (gated && (rc = ed_launch(d, b, n, stream, nullptr, nullptr, true, b.m_state.as<uint32_t>(), ED_CALL))) return rc;
+    NWV_HIP(hipMemcpyAsync(st, b.m_state.p, 8, hipMemcpyDeviceToHost, stream));
+    if (gated) NWV_HIP(hipMemcpyAsync(bits, b.verdict.p, 8 * ((n + 63) / 64), hipMemcpyDeviceToHost, stream));
+    NWV_HIP(hipStreamSynchronize(stream));
+    if (gated) htrace("batch:gated-done");
+    const bool accepted = st[1] == 1;
+    if (accepted && bits) accept_all(bits, n);
+    if (accepted || gated) *ok = (accepted || verdicts_all_valid(bits, n)) ? 1 : 0;
+    else if (!bits && st[1] == 0) *ok = 0;
+    else *decided = false;
+    return NWV_OK;
+}
+
+// Batch verdict of resident buffers by the path that staging planned (b.plan, ed_plan.h); bits: the
+// shard's verdict words (may be null).  Tiny and Comb give exact bits in one launch.  A batch of
+// valid signatures always passes the MSM (the cofactored equation holds for each term whatever z_i),
+// so its rejection is final for a caller that only wants the batch verdict.
+static int batch_on_device(Lane& d, EdBuffers& b, size_t n, const uint8_t seed[32], hipStream_t stream,
+                           int* ok, uint64_t* bits, bool state_ready) {
+    bool decided = false;
+    switch (b.plan.path) {
+    case EdPath::Tiny:
+        d.gpu->n_tiny++;
+        return tiny_on_device(d, b, n, stream, ok, bits, nullptr);
+    case EdPath::Comb:
+        d.gpu->n_comb++;
+        return comb_on_device(d, b, n, stream, ok, bits, nullptr);
+    case EdPath::Msm:
+        if (const int rc = msm_on_device(d, b, n, seed, stream, state_ready, ok, bits, &decided); rc || decided) return rc;
+        return each_on_device(d, b, n, stream, ok, bits, true);
+    case EdPath::Each:
+        break;
+    }
+    return each_on_device(d, b, n, stream, ok, bits, false);
+}
+
+// One range of a batch call on its lane, after staging: its verdict, merged into the call's.  Every
+// path of batch_on_device ends with the stream synchronised: kc_call_done (no-op without a hold).
+static int run_range(Lane& d, size_t lo, size_t n, const uint8_t seed[32], std::mutex& mu, int* all_valid,
+                     uint64_t* bits) {
+    int ok = 1;
+    const int rc = batch_on_device(d, d.ed, n, seed, d.stream, &ok, bits ? bits + lo / 64 : nullptr, true);
+    if (rc) return rc;
+    kc_call_done(d);
+    std::lock_guard<std::mutex> g(mu);
+    if (!ok) *all_valid = 0;
     return NWV_OK;
 }
 
@@ -2278,27 +2245,25 @@ int nwv_ed25519_verify_batch(nwv_ctx* ctx, size_t n, const uint8_t* pk, const ui
         return set_err(NWV_ERR_ARG, "null argument");
     *all_valid = 1;
     if (n == 0) return NWV_OK;
-    for (size_t i = 0; i < n; i++)
-        if (msg_len[i] && !msg_base) return set_err(NWV_ERR_ARG, "null msg_base");
+    if (int rc = check_msg_base(n, msg_base, msg_len)) return rc;
     uint8_t seed[32];
     fill_seed(seed32, seed);
     std::mutex omu;
-    int rc = for_shards(ctx, n, [&](Lane& d, size_t lo, size_t hi) -> int {
-        // each shard gets its own coefficient stream: seed' = seed with the shard start mixed in
+    return for_shards(ctx, n, [&](Lane& d, size_t lo, size_t hi) -> int {
         uint8_t s2[32];
-        std::memcpy(s2, seed, 32);
-        for (int k = 0; k < 8; k++) s2[24 + k] ^= (uint8_t)((uint64_t)lo >> (8 * k));
-        int r = ed_stage(d, d.ed, lo, hi, pk, sig, msg_base, msg_off, msg_len, s2);
-        if (r) return r;
-        int ok = 1;
-        r = batch_on_device(d, d.ed, hi - lo, s2, d.stream, &ok,
-                            verdict_bits_or_null ? verdict_bits_or_null + lo / 64 : nullptr, true);
-        if (r) return r;
-        std::lock_guard<std::mutex> g(omu);
-        if (!ok) *all_valid = 0;
-        return NWV_OK;
+        shard_seed(seed, lo, s2);
+        const int r = ed_stage(d, d.ed, EdBatch{sig, msg_base, msg_off, msg_len, lo, hi}, pk, s2, nullptr, StageOpts{});
+        return r ? r : run_range(d, lo, hi - lo, s2, omu, all_valid, verdict_bits_or_null);
     });
-    return rc;
+}
+
+// A keyed call's staging options.  The comb path is offered to single-range calls only: a call that
+// splits over the devices keeps the MSM on every shard
+static StageOpts keyed_opts(const nwv_ctx* ctx, size_t n, bool kc_lookup_only) {
+    StageOpts o;
+    o.kc_lookup_only = kc_lookup_only;
+    o.comb_max = nwv::ed_shard_ranges(n, ctx->devs.size(), ctx->shard_min).size() == 1 ? ctx->comb_batch_max.load() : 0;
+    return o;
 }
 
 static int verify_batch_keyed_impl(nwv_ctx* ctx, size_t n_keys, const uint8_t* keys, size_t n,
@@ -2310,30 +2275,16 @@ static int verify_batch_keyed_impl(nwv_ctx* ctx, size_t n_keys, const uint8_t* k
         return set_err(NWV_ERR_ARG, "null argument");
     *all_valid = 1;
     if (n == 0) return NWV_OK;
-    for (size_t i = 0; i < n; i++)
-        if (msg_len[i] && !msg_base) return set_err(NWV_ERR_ARG, "null msg_base");
+    if (int rc = check_msg_base(n, msg_base, msg_len)) return rc;
     uint8_t seed[32];
     fill_seed(seed32, seed);
     std::mutex omu;
-    // the comb path is offered to single-range calls only: a call that splits over the devices
-    // keeps the MSM on every shard
-    const size_t comb_max =
-        nwv::ed_shard_ranges(n, ctx->devs.size(), ctx->shard_min).size() == 1 ? ctx->comb_batch_max.load() : 0;
+    const StageOpts opt = keyed_opts(ctx, n, kc_lookup_only);
     return for_shards(ctx, n, [&](Lane& d, size_t lo, size_t hi) -> int {
         uint8_t s2[32];
-        std::memcpy(s2, seed, 32);
-        for (int k = 0; k < 8; k++) s2[24 + k] ^= (uint8_t)((uint64_t)lo >> (8 * k));
-        int r = ed_stage_keyed(d, d.ed, lo, hi, n_keys, keys, key_idx, sig, msg_base, msg_off, msg_len, s2,
-                               nullptr, kc_lookup_only, comb_max);
-        if (r) return r;
-        int ok = 1;
-        r = batch_on_device(d, d.ed, hi - lo, s2, d.stream, &ok,
-                            verdict_bits_or_null ? verdict_bits_or_null + lo / 64 : nullptr, true);
-        if (r) return r;
-        kc_call_done(d);  // every path of batch_on_device ends with the stream synchronised
-        std::lock_guard<std::mutex> g(omu);
-        if (!ok) *all_valid = 0;
-        return NWV_OK;
+        shard_seed(seed, lo, s2);
+        const int r = ed_stage_keyed(d, d.ed, EdBatch{sig, msg_base, msg_off, msg_len, lo, hi}, n_keys, keys, key_idx, s2, opt);
+        return r ? r : run_range(d, lo, hi - lo, s2, omu, all_valid, verdict_bits_or_null);
     });
 }
 
@@ -2375,19 +2326,16 @@ int nwv_ed25519_verify_batch_grouped(nwv_ctx* ctx, size_t n, const uint8_t* pk, 
         return nwv_ed25519_verify_batch(ctx, n, pk, sig, msg_base, msg_off, msg_len, seed32, all_valid,
                                         verdict_bits_or_null);
     }
-    for (size_t i = 0; i < n && !msg_base; i++)
-        if (msg_len[i]) return set_err(NWV_ERR_ARG, "null msg_base");
+    if (int rc = check_msg_base(n, msg_base, msg_len)) return rc;
     uint8_t seed[32];
     fill_seed(seed32, seed);
     std::mutex omu;
-    const size_t comb_max =
-        nwv::ed_shard_ranges(n, ctx->devs.size(), ctx->shard_min).size() == 1 ? ctx->comb_batch_max.load() : 0;
-    int how_call = 1;  // the call counts as its least keyed range: 1 cached, 2 keyed uncached, 3 un-keyed
+    const StageOpts opt = keyed_opts(ctx, n, true);
+    std::atomic<int> hows{0};  // bit `how` of every range that ran: 1 cached, 2 keyed uncached, 3 un-keyed
     int rc = for_shards(ctx, n, [&](Lane& d, size_t lo, size_t hi) -> int {
         const size_t cnt = hi - lo;
         uint8_t s2[32];
-        std::memcpy(s2, seed, 32);
-        for (int k = 0; k < 8; k++) s2[24 + k] ^= (uint8_t)((uint64_t)lo >> (8 * k));
+        shard_seed(seed, lo, s2);
         thread_local nwv::KeyGrouper kg;  // per-thread scratch, as ed_stage_keyed's
         const uint8_t* rpk = pk + 32 * lo;
         int how = 3;
@@ -2396,25 +2344,19 @@ int nwv_ed25519_verify_batch_grouped(nwv_ctx* ctx, size_t n, const uint8_t* pk, 
             how = 2;
         int r;
         if (how == 3) {
-            r = ed_stage(d, d.ed, lo, hi, pk, sig, msg_base, msg_off, msg_len, s2);
+            r = ed_stage(d, d.ed, EdBatch{sig, msg_base, msg_off, msg_len, lo, hi}, pk, s2, nullptr, StageOpts{});
         } else {
             // (the range's own arrays from index 0: key_idx is the range's)
-            r = ed_stage_keyed(d, d.ed, 0, cnt, kg.n_distinct(), kg.distinct(), kg.key_idx(), sig + 64 * lo, msg_base,
-                               msg_off + lo, msg_len + lo, s2, nullptr, true, comb_max);
+            r = ed_stage_keyed(d, d.ed, EdBatch{sig + 64 * lo, msg_base, msg_off + lo, msg_len + lo, 0, cnt},
+                               kg.n_distinct(), kg.distinct(), kg.key_idx(), s2, opt);
             if (!r && d.ed.kc_split) how = 1;
         }
-        if (r) return r;
-        int ok = 1;
-        r = batch_on_device(d, d.ed, cnt, s2, d.stream, &ok,
-                            verdict_bits_or_null ? verdict_bits_or_null + lo / 64 : nullptr, true);
-        if (r) return r;
-        kc_call_done(d);  // every path of batch_on_device ends with the stream synchronised
-        std::lock_guard<std::mutex> g(omu);
-        if (!ok) *all_valid = 0;
-        how_call = std::max(how_call, how);
+        if (r || (r = run_range(d, lo, cnt, s2, omu, all_valid, verdict_bits_or_null))) return r;
+        hows |= 1 << how;
         return NWV_OK;
     });
-    if (rc == NWV_OK) ctx->n_grouped[how_call]++;
+    // the call counts as its least keyed range
+    if (rc == NWV_OK) ctx->n_grouped[hows & 8 ? 3 : hows & 4 ? 2 : 1]++;
     return rc;
 }
 
@@ -2467,7 +2409,7 @@ int nwv_keycache_register(nwv_ctx* ctx, size_t n_keys, const uint8_t* keys) {
         kc_hold_excl(*lane);
         std::vector<uint32_t> slots, all;
         for (size_t a = 0; a < n_keys && !rc; a += 4096) {
-            rc = keycache_slots(*lane, keys + 32 * a, std::min<size_t>(4096, n_keys - a), slots);
+            rc = keycache_slots(*lane, keys + 32 * a, std::min<size_t>(4096, n_keys - a), slots, false);
             all.insert(all.end(), slots.begin(), slots.end());
         }
         if (rc) return rc;
@@ -2706,7 +2648,7 @@ int nwv_stage_ed25519(nwv_ctx* ctx, int device_index, size_t n, const uint8_t* p
                       const uint8_t* sig, const uint8_t* msg_base, const uint64_t* msg_off,
                       const uint32_t* msg_len, nwv_staged** out) {
     return staged_create(ctx, device_index, n, out, [&](Lane& d, EdBuffers& b) {
-        return ed_stage(d, b, 0, n, pk, sig, msg_base, msg_off, msg_len, nullptr);
+        return ed_stage(d, b, EdBatch{sig, msg_base, msg_off, msg_len, 0, n}, pk, nullptr, nullptr, StageOpts{});
     });
 }
 
@@ -2715,9 +2657,12 @@ int nwv_stage_ed25519_keyed(nwv_ctx* ctx, int device_index, size_t n_keys, const
                             const uint64_t* msg_off, const uint32_t* msg_len, nwv_staged** out) {
     if (n && (!keys || !key_idx || !sig || !msg_off || !msg_len)) return set_err(NWV_ERR_ARG, "null argument");
     std::vector<uint32_t> pinned;
+    // pin_out marks the batch as staged: nwv_staged_run launches the MSM or the per-signature
+    // pipeline itself and never consults a plan, so the buffers keep the default one (ed_plan.h)
+    StageOpts opt;
+    opt.pin_out = &pinned;
     const int rc = staged_create(ctx, device_index, n, out, [&](Lane& d, EdBuffers& b) {
-        return ed_stage_keyed(d, b, 0, n, n_keys, keys, key_idx, sig, msg_base, msg_off, msg_len, nullptr, nullptr, false,
-                              0, &pinned);
+        return ed_stage_keyed(d, b, EdBatch{sig, msg_base, msg_off, msg_len, 0, n}, n_keys, keys, key_idx, nullptr, opt);
     });
     if (pinned.empty()) return rc;
     if (rc) {
@@ -2901,8 +2846,7 @@ int nwv_staged_fetch(nwv_staged* st, uint64_t* verdict_bits, int* all_valid) {
         NWV_HIP(hipMemcpyAsync(state, st->buf.m_state.p, 8, hipMemcpyDeviceToHost, st->stream));
         NWV_HIP(hipStreamSynchronize(st->stream));
         if (state[1] == 1) {
-            std::memset(bits, 0, 8 * words);
-            set_ones(bits, 0, st->n);
+            accept_all(bits, st->n);
             if (all_valid) *all_valid = 1;
             return NWV_OK;
         }
@@ -3212,19 +3156,19 @@ static int keyed_digests_run(nwv_ctx* ctx, size_t n_pre, const uint8_t* pre_base
     for (size_t k = 0; k < n_pre; k++) maxlen = std::max<uint64_t>(maxlen, pre_len[k]);
     // the batch is staged before the hash launch (its copy does not depend on the digests), so
     // hash and verification run back to back; no host round trip between them
-    rc = ed_stage_keyed(d, d.ed, 0, n, n_keys, keys, key_idx, sig, nullptr, moff.data(), mlen.data(), seed,
-                        &d.b2_out, false, ctx->comb_batch_max.load());  // (a single range, see above)
+    StageOpts opt;
+    opt.dev_msg = &d.b2_out;
+    opt.comb_max = ctx->comb_batch_max.load();  // (a single range, see above)
+    rc = ed_stage_keyed(d, d.ed, EdBatch{sig, /*msg_base*/ nullptr, moff.data(), mlen.data(), 0, n}, n_keys, keys,
+                        key_idx, seed, opt);
     if (rc) return rc;
     // the hash also writes the digests straight into coherent pinned host memory (no copy back)
     if ((rc = d.b2dig.ensure(32 * n_pre, hipHostMallocCoherent | hipHostMallocMapped))) return rc;
     b2_launch(d, n_pre, maxlen, st.base, st.off, st.len, d.b2_out.as<uint32_t>(), static_cast<uint32_t*>(d.b2dig.p));
     NWV_HIP(hipGetLastError());
-    int ok = 1;
-    rc = batch_on_device(d, d.ed, n, seed, d.stream, &ok, verdict_bits_or_null, true);
-    if (rc) return rc;
-    if (!ok) *all_valid = 0;
-    NWV_HIP(hipStreamSynchronize(d.stream));  // already synchronised by the verdict read
-    kc_call_done(d);
+    std::mutex mu;  // (a single range)
+    if ((rc = run_range(d, 0, n, seed, mu, all_valid, verdict_bits_or_null))) return rc;
+    NWV_HIP(hipStreamSynchronize(d.stream));  // already synchronised by the verdict read (so kc_call_done there)
     std::memcpy(digests_out, d.b2dig.p, 32 * n_pre);
     return NWV_OK;
 }
@@ -3296,11 +3240,14 @@ static int typed_fused_run(nwv_ctx* ctx, Lane& d, size_t n_pre, const uint8_t* p
             src[i] = (m + 1u) | (first[m] == (uint32_t)i ? nwv::TYPED_SRC_STORE : 0u);
         }
     }
-    int rc = ed_stage_keyed(d, d.ed, 0, n, n_keys, keys, key_idx, sig, ar.data(), moff.data(), mlen.data(), seed,
-                            nullptr, false, ctx->comb_batch_max.load(), nullptr, span);
+    StageOpts opt;
+    opt.msg_span = span;
+    opt.comb_max = ctx->comb_batch_max.load();
+    int rc = ed_stage_keyed(d, d.ed, EdBatch{sig, ar.data(), moff.data(), mlen.data(), 0, n}, n_keys, keys, key_idx,
+                            seed, opt);
     if (rc) return rc;
-    const bool tiny = n <= (size_t)TINY_MAX;
-    if (tiny ? !d.ed.tiny : !d.ed.comb) return NWV_OK;
+    const bool tiny = d.ed.plan.path == EdPath::Tiny;
+    if (!tiny && d.ed.plan.path != EdPath::Comb) return NWV_OK;
     // the digests come back in coherent pinned memory: slot j of the first n_pre for a short digest
     // that a signature stored, slot n_pre + k for entry k of the side list
     if ((rc = d.b2dig.ensure(32 * (n_pre + ns) + 32, hipHostMallocCoherent | hipHostMallocMapped)) ||
@@ -3373,7 +3320,7 @@ int nwv_ed25519_verify_batch_typed(nwv_ctx* ctx, size_t n_pre, const uint8_t* pr
             Lane& d = *lane;
             int rc = lane.rc();
             if (rc) return rc;
-            if (!(d.flags & (NWV_FLAG_NO_TINY | NWV_FLAG_MSM_ALWAYS | NWV_FLAG_MSM_NEVER))) {
+            if (!(d.flags & nwv::ED_FORCES_PATH)) {
                 int took = 0;
                 *all_valid = 1;
                 rc = typed_fused_run(ctx, d, n_pre, pre_base, pre_off, pre_len, pre_short, digests_out, n_lit, lits,
@@ -3433,7 +3380,7 @@ int nwv_ed25519_sign_many(nwv_ctx* ctx, size_t n, const uint8_t* seeds, const ui
     if (!msg_base) msg_base = empty;
     return for_shards_fixed(ctx, n, [&](Lane& d, size_t lo, size_t hi) -> int {
         // messages via the Ed25519 staging; seeds go to kbuf, outputs come back in pk / sig
-        int rc = ed_stage(d, d.ed, lo, hi, nullptr, nullptr, msg_base, msg_off, msg_len, nullptr);
+        int rc = ed_stage(d, d.ed, EdBatch{nullptr, msg_base, msg_off, msg_len, lo, hi}, nullptr, nullptr, nullptr, StageOpts{});
         if (rc) return rc;
         const size_t m = hi - lo;
         if ((rc = d.ed.kbuf.ensure(32 * m + 16))) return rc;
